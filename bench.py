@@ -5,15 +5,22 @@ SGD update), batch 32 per GPU, bf16, random-init net (levels 2, width 1.0, K=3),
     python bench.py --gpus N --steps K --warmup W            (N > 1: starts N rank processes itself, see self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --mode infer [--image-side 4096]         BASELINE.json configs[2] / [4]: tiled inference, Mpx/s
+    ... --full                                               everything listed below the headline fields
+    ... --dump-outputs DIR                                   what the last timed step computed, as DIR/<name>.npy
 
 One process per GPU; for N > 1 the only exchange step of the path is the all-reduce (RCCL) of the flat gradient
 bucket (training) / of the cross-rank overlap sums (inference).  Inputs are resident in HBM before the timed region.
 Before the W warm-up steps the workload runs untimed for `prewarm_s` seconds (declared in the line) so that the clocks have
-settled when a short --steps / --warmup run is timed.  The default (training) line also carries an `infer` object: tiled
-inference over a 4096^2 image (BASELINE.json configs[2]; 16384^2 = configs[4] for N > 1), measured by a child process that
-runs `bench.py --mode infer` after the training measurement has finished (a failure there is reported inside `infer`, it
-cannot take the training line with it).
-Prints ONE JSON line on rank 0, with
+settled when a short --steps / --warmup run is timed.  The trainer then returns to its state right after Initialize, so that
+the K timed steps compute the same results from run to run whatever the pre-warm ran (--dump-outputs writes params.npy,
+running_stats.npy and loss.npy; in infer mode labels.npy, the label map or a fixed sample of it).
+A plain run does only that and prints the headline fields (metric, value, unit, ms_per_step, dtype, config, ranks_seen /
+devices = an all-reduce of ones and the device index of every rank).  With --full the timed region also carries the
+profiler's event pairs on the dominant conv entry (sampled), and the line the objects below.  The --full training line also
+carries an `infer` object: tiled inference over a 4096^2 image (BASELINE.json configs[2]; 16384^2 = configs[4] for N > 1),
+measured by a child process that runs `bench.py --mode infer --full` after the training measurement has finished (a failure
+there is reported inside `infer`, it cannot take the training line with it).
+Prints ONE JSON line on rank 0; with --full it also holds
   roofline     — the §8d conv entry (layer x pass) with the largest time: algorithmic flops and minimum bytes per launch
                   / its mean launch time, measured with HIP events on the compute stream inside the
                  timed region; `traffic` = HBM-side bytes per launch from the committed rocprofv3 --pmc passes;
@@ -21,16 +28,17 @@ Prints ONE JSON line on rank 0, with
                  §8d flops and minimum bytes, bound = min(MFMA, AI x HBM), fraction of that bound;
   overhead_kernels — everything in the step that is not a §8d conv pass (bn finalize / apply, partial sums, SGD ...);
   cpu_baseline — the oracle (a CPU port of the path, see oracle/) timed on this host on a bounded sample, all threads and
-                 one thread, plus a PyTorch-CPU (oneDNN) figure of the same net as a second, clearly labelled baseline;
-  ranks_seen / devices — an all-reduce of ones and the device index of every rank.
+                 one thread, plus a PyTorch-CPU (oneDNN) figure of the same net as a second, clearly labelled baseline.
 """
 import argparse
 import json
 import os
 import re
+import shutil
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -421,6 +429,41 @@ def prewarm(run_once, sync, seconds, agree=None):
         sync()
 
 
+def save_initial_state(t):
+    """The trainer's whole state right after Initialize (weights, momentum, bn running statistics and their update counters, the
+    learning-rate schedule) in a temporary file.  The pre-warm runs for a time, not a step count, so the timed steps start from this
+    state again (restore_initial_state): with the same arguments they then compute the same outputs from run to run."""
+    path = os.path.join(tempfile.mkdtemp(prefix="anh_bench_"), "initial.state")
+    t.save_state(path)
+    return path
+
+
+def restore_initial_state(t, path):
+    t.load_state(path)
+    shutil.rmtree(os.path.dirname(path), ignore_errors=True)
+
+
+def dump_training_outputs(t, out_dir):
+    """--dump-outputs: what the caller of the training step holds after the last timed step (weights, bn running statistics, loss)."""
+    os.makedirs(out_dir, exist_ok=True)
+    params, running = t.get_params()
+    np.save(os.path.join(out_dir, "params.npy"), params)
+    np.save(os.path.join(out_dir, "running_stats.npy"), running)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([t.get_last_loss()], dtype=np.float64))
+
+
+def dump_label_map(labels, out_dir, limit=1 << 22):
+    """--dump-outputs, inference: the label map annonet_infer() returns, as float32 — whole up to `limit` pixels, beyond that the
+    pixels at a fixed, seeded set of flat indices (the same for every run of one image size)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    flat = labels.reshape(-1)
+    if flat.numel() > limit:
+        idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), limit))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(out_dir, "labels.npy"), flat.to(torch.float32).cpu().numpy())
+
+
 def make_agree(torch, dist, dev, use_dist):
     if not use_dist:
         return None
@@ -432,7 +475,7 @@ def make_agree(torch, dist, dev, use_dist):
     return agree
 
 
-def infer_one_size(args, side, with_cpu_baseline, aa, aad, torch, dist, prec, rank, local_rank, world, use_dist):
+def infer_one_size(args, side, with_cpu_baseline, dump_dir, aa, aad, torch, dist, prec, rank, local_rank, world, use_dist):
     """One image size of the inference bench -> the result object (rank 0) or None."""
     dev = torch.device("cuda", local_rank)
     cfg = aa.net_config(LEVELS, 3, CLASSES, WIDTH, 1, prec)
@@ -461,7 +504,7 @@ def infer_one_size(args, side, with_cpu_baseline, aa, aad, torch, dist, prec, ra
     # N > 1, labels on the host: ONE host map per label set in POSIX shared memory, every rank delivering the cells of its own tiles over
     # its own PCIe link (dist.HostLabelMap) — rank 0 copies only its share, nothing is gathered first
     host_maps = None
-    if world > 1:
+    if world > 1 and args.full:
         host_maps = []
         for _ in range(2):
             names = [None]
@@ -523,28 +566,43 @@ def infer_one_size(args, side, with_cpu_baseline, aa, aad, torch, dist, prec, ra
     prewarm_passes = prewarm(run, torch.cuda.synchronize, args.prewarm_s, make_agree(torch, dist, dev, use_dist))
     for _ in range(max(args.warmup, 1)):
         run()
-    # untimed profile pass: every kernel class of one image
-    net.synchronize()
-    net.profile_enable(True)
-    run()
-    net.synchronize()
-    prof_all = net.profile()
-    if args.dump_launch_order and rank == 0:
-        with open(args.dump_launch_order, "w") as f:
-            json.dump({"order": net.profile_launch_order()}, f, indent=0)
-    net.profile_reset()
-    if os.environ.get("ANH_BENCH_VERBOSE") and rank == 0:   # every kernel class of one image, serialised by the event pairs
-        for e in sorted(prof_all, key=lambda e: -e["total_ms"]):
-            print(f"  {e['name']:52s} {e['total_ms']:8.3f} ms/image  {e['launches']:4d} launches", file=sys.stderr)
     win = aa.RuntimeNet.GetRecommendedInputDimension(LEVELS, tiles[0][0][2] - tiles[0][0][0] + 1)   # side of a tile's input window
-    layers, dims = layer_geometry(aa, cfg, win)
-    convs = [e for e in prof_all if ENTRY_RE.search(e["name"]) and layers[int(ENTRY_RE.search(e["name"]).group(2))].k > 1]
-    dominant = max(convs, key=lambda e: e["total_ms"])["name"] if convs else ""
-    # Both timed regions run under the SAME instrumentation (event pairs on the dominant conv entry only) and the same step count:
-    # `value` with image and label map resident, `value_labels_on_host` with the label map copied to pinned host memory per pass.
-    net.profile_set_filter(dominant)
+    if args.full:
+        # untimed profile pass: every kernel class of one image
+        net.synchronize()
+        net.profile_enable(True)
+        run()
+        net.synchronize()
+        prof_all = net.profile()
+        if args.dump_launch_order and rank == 0:
+            with open(args.dump_launch_order, "w") as f:
+                json.dump({"order": net.profile_launch_order()}, f, indent=0)
+        net.profile_reset()
+        if os.environ.get("ANH_BENCH_VERBOSE") and rank == 0:   # every kernel class of one image, serialised by the event pairs
+            for e in sorted(prof_all, key=lambda e: -e["total_ms"]):
+                print(f"  {e['name']:52s} {e['total_ms']:8.3f} ms/image  {e['launches']:4d} launches", file=sys.stderr)
+        layers, dims = layer_geometry(aa, cfg, win)
+        convs = [e for e in prof_all if ENTRY_RE.search(e["name"]) and layers[int(ENTRY_RE.search(e["name"]).group(2))].k > 1]
+        dominant = max(convs, key=lambda e: e["total_ms"])["name"] if convs else ""
+        # Both timed regions run under the SAME instrumentation (event pairs on the dominant conv entry only) and the same step count:
+        # `value` with image and label map resident, `value_labels_on_host` with the label map copied to pinned host memory per pass.
+        net.profile_set_filter(dominant)
     elapsed = timed(args.steps)
     net.synchronize()
+    if dump_dir and rank == 0:
+        dump_label_map(labels, dump_dir)
+    out = None
+    if rank == 0:
+        out = {"metric": f"Mpixels/s tiled inference, {side}x{side} image, 1024^2 tiles, overlap {ov}", "value": side * side * args.steps / elapsed / 1e6,
+               "unit": "Mpx/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "prewarm_s": args.prewarm_s if prewarm_passes else 0.0,
+               "ms_per_step": 1e3 * elapsed / args.steps,
+               "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+               "config": {"workload": f"annonet_infer(): {side}x{side} image, {len(tiles)} tiles ({len(mine)} on rank 0), window {win}, levels={LEVELS} width={WIDTH} K={CLASSES}",
+                          "parallelism": f"tile-shard{world}", "exchanged_pixels": exchange.pixels()},
+               "ranks_seen": ranks_seen, "devices": devices}
+    if not args.full:
+        torch.cuda.synchronize()
+        return out
     dom = [e for e in net.profile() if e["name"] == dominant]
     elapsed_host = timed(args.steps, to_host=True)
     net.synchronize()
@@ -559,7 +617,6 @@ def infer_one_size(args, side, with_cpu_baseline, aa, aad, torch, dist, prec, ra
             raise SystemExit(f"host label map: the ranks' cells cover {sum(gathered)} bytes of {side * side * 2}")
         for hm in host_maps:
             hm.close()
-    out = None
     if rank == 0:
         roof = None
         if dom and dom[0]["launches"]:
@@ -584,17 +641,12 @@ def infer_one_size(args, side, with_cpu_baseline, aa, aad, torch, dist, prec, ra
                         arithmetic_intensity=flops / min_bytes, bytes_convention="SURVEY 8d minimum: one input + output + filters (skip operand not counted)")
         total_ms = sum(e["total_ms"] for e in prof_all) or 1.0
         share = sorted(((e["name"], round(100 * e["total_ms"] / total_ms, 1)) for e in prof_all), key=lambda x: -x[1])[:10]
-        out = {"metric": f"Mpixels/s tiled inference, {side}x{side} image, 1024^2 tiles, overlap {ov}", "value": side * side * args.steps / elapsed / 1e6,
-               "unit": "Mpx/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "prewarm_s": args.prewarm_s if prewarm_passes else 0.0,
-               "ms_per_step": 1e3 * elapsed / args.steps,
-               "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
-               "config": {"workload": f"annonet_infer(): {side}x{side} image, {len(tiles)} tiles ({len(mine)} on rank 0), window {win}, levels={LEVELS} width={WIDTH} K={CLASSES}",
-                          "parallelism": f"tile-shard{world}", "exchanged_pixels": exchange.pixels(),
-                          "host_bytes_per_rank": host_bytes},
-               "value_labels_on_host": side * side * args.steps / elapsed_host / 1e6,
-               "value_note": "value: image and label map resident in HBM (N > 1: ONE map assembled on rank 0, dist.LabelGather); value_labels_on_host: the same passes with the label map copied to pinned host memory inside the timed region (N > 1: every rank copies the cells of its own tiles into ONE shared-memory host map over its own PCIe link, dist.HostLabelMap: config.host_bytes_per_rank) (SURVEY 8d's unit; two label maps used alternately, so the copy of one image overlaps the passes of the next; every copy ends inside the region); same step count and instrumentation",
-               "roofline": roof, "kernel_time_share_pct": share, "ranks_seen": ranks_seen, "devices": devices,
-               "cpu_baseline": cpu_baseline_infer(aa, cfg, ov) if with_cpu_baseline else None}
+        out["config"]["host_bytes_per_rank"] = host_bytes
+        out.update({
+            "value_labels_on_host": side * side * args.steps / elapsed_host / 1e6,
+            "value_note": "value: image and label map resident in HBM (N > 1: ONE map assembled on rank 0, dist.LabelGather); value_labels_on_host: the same passes with the label map copied to pinned host memory inside the timed region (N > 1: every rank copies the cells of its own tiles into ONE shared-memory host map over its own PCIe link, dist.HostLabelMap: config.host_bytes_per_rank) (SURVEY 8d's unit; two label maps used alternately, so the copy of one image overlaps the passes of the next; every copy ends inside the region); same step count and instrumentation",
+            "roofline": roof, "kernel_time_share_pct": share,
+            "cpu_baseline": cpu_baseline_infer(aa, cfg, ov) if with_cpu_baseline else None})
     torch.cuda.synchronize()
     return out
 
@@ -608,12 +660,13 @@ def bench_infer(args, aa, aad, torch, dist, prec, rank, local_rank, world, use_d
     sides = [int(x) for x in str(args.image_side).split(",")]
     out = None
     for i, side in enumerate(sides):
-        res = infer_one_size(args, side, i == 0 and not args.no_cpu_baseline and world == 1, aa, aad, torch, dist, prec, rank, local_rank, world, use_dist)
+        res = infer_one_size(args, side, i == 0 and not args.no_cpu_baseline and world == 1, args.dump_outputs if i == 0 else None,
+                             aa, aad, torch, dist, prec, rank, local_rank, world, use_dist)
         if rank == 0:
             if i == 0:
                 out = res
             else:
-                out.setdefault("other_sizes", []).append({k: res[k] for k in ("metric", "value", "value_labels_on_host", "ms_per_step", "steps", "config", "roofline")})
+                out.setdefault("other_sizes", []).append({k: res[k] for k in ("metric", "value", "value_labels_on_host", "ms_per_step", "steps", "config", "roofline") if k in res})
     if rank == 0:
         print(json.dumps(out), flush=True)
     if use_dist:
@@ -627,7 +680,7 @@ def infer_in_child(args, world):
     the timeout — stays inside the returned object."""
     sides = args.infer_sides or ("4096,16384" if world == 1 else "16384")
     cmd = [sys.executable, os.path.abspath(__file__), "--mode", "infer", "--gpus", str(world), "--image-side", sides, "--steps", str(args.infer_steps),
-           "--warmup", "2", "--precision", args.precision, "--prewarm-s", str(min(args.prewarm_s, 1.0))]
+           "--warmup", "2", "--precision", args.precision, "--prewarm-s", str(min(args.prewarm_s, 1.0)), "--full"]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if args.backend != "nccl":
@@ -665,6 +718,7 @@ def bench_in_process(args):
     t.SetClassCount(CLASSES)
     t.Initialize()
     t.SetLearningRate(0.1)
+    initial_state = save_initial_state(t)
     imgs, wls = [], []
     for r in range(R):   # replica r gets the shard rank r of the one-process-per-GPU job would hold
         img, lab, _ = synthetic_batch(r)
@@ -680,6 +734,7 @@ def bench_in_process(args):
     for _ in range(max(args.warmup, 1)):
         step()
     t.synchronize()
+    restore_initial_state(t, initial_state)
     t.reset_exchange_stats()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -687,6 +742,8 @@ def bench_in_process(args):
     t.synchronize()
     elapsed = time.perf_counter() - t0
     st = t.exchange_stats()
+    if args.dump_outputs:
+        dump_training_outputs(t, args.dump_outputs)
     out = {"metric": "227x227 RGB tiles/sec fwd+bwd @ batch 32 per GPU, one process driving all GPUs (anh_set_devices), host vectors every step",
            "value": n * args.steps / elapsed, "unit": "tiles/s", "n_gpus": len(set(devices)), "replicas": R, "devices": devices, "steps": args.steps, "warmup": args.warmup,
            "prewarm_s": args.prewarm_s if prewarm_steps else 0.0, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
@@ -726,27 +783,36 @@ def in_process_child(args, world):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 200 train, 20 infer)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps (default: 20 train, 3 infer)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the profile pass and roofline / per-layer "
+                    "tables, the host-input rate, the CPU baselines, the `infer` object, and at N > 1 `exchange` and `in_process`")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--mode", default="train", choices=["train", "infer"], help="train = BASELINE.json's metric (default); infer = tiled inference over a 4096x4096 image")
     ap.add_argument("--image-side", default="4096", help="infer mode: image side, or a comma list (the first is the line, the others ride in other_sizes)")
     ap.add_argument("--prewarm-s", type=float, default=PREWARM_S, help="untimed time-based pre-warm before the warm-up steps (declared in the line)")
-    ap.add_argument("--no-infer", action="store_true", help="train mode: leave the `infer` object out (profile collection under rocprofv3)")
+    ap.add_argument("--no-infer", action="store_true", help="train mode with --full: leave the `infer` object out (profile collection under rocprofv3)")
     ap.add_argument("--infer-steps", type=int, default=10)
     ap.add_argument("--infer-sides", default=None, help="image sides of the `infer` object (default: 4096,16384 at one GPU = BASELINE.json configs[2], 16384 = configs[4] otherwise)")
     ap.add_argument("--infer-timeout", type=float, default=300.0)
     ap.add_argument("--collective-timeout", type=float, default=180.0, help="seconds after which a collective that a rank never joined fails the job")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend: nccl = RCCL over xGMI (the job); gloo = rehearsal transport")
     ap.add_argument("--one-gpu", action="store_true", help="rehearsal of the N > 1 paths on a one-GPU box: every rank drives device 0 (needs --backend gloo: RCCL wants one GPU per rank)")
-    ap.add_argument("--no-in-process", action="store_true", help="N > 1: leave the `in_process` object (host B measured by a child process) out")
+    ap.add_argument("--no-in-process", action="store_true", help="N > 1 with --full: leave the `in_process` object (host B measured by a child process) out")
     ap.add_argument("--in-process", action="store_true", help="host (B): ONE process drives --gpus N devices (or --devices) through anh_set_devices and StartTraining with host vectors; prints its own line")
     ap.add_argument("--devices", default=None, help="--in-process: explicit device list, e.g. 0,0 = two replicas rehearsed on one GPU")
-    ap.add_argument("--dump-launch-order", default=None, help="write the step's launch order (profiler entry per kernel-class launch) as JSON: input of tools/pmc_traffic.py")
+    ap.add_argument("--dump-launch-order", default=None, help="with --full: write the step's launch order (profiler entry per kernel-class launch) as JSON: input of tools/pmc_traffic.py")
     args = ap.parse_args()
-    if args.mode == "infer" and args.steps == 200:
-        args.steps, args.warmup = 20, 3
+    if args.steps is None:
+        args.steps = 20 if args.mode == "infer" else 200
+    if args.warmup is None:
+        args.warmup = 3 if args.mode == "infer" else 20
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_launch_order and not args.full:
+        ap.error("--dump-launch-order comes from the profile pass: it needs --full")
 
     if args.in_process:
         return bench_in_process(args)
@@ -789,6 +855,7 @@ def main():
     t.SetClassCount(CLASSES)
     t.Initialize()
     t.SetLearningRate(0.1)
+    initial_state = save_initial_state(t)
     t_stream = aad.handle_stream(t)       # torch's view of the trainer's own stream: the all-reduce is enqueued there
     bucket = aad.grad_bucket_tensor(t)
 
@@ -813,29 +880,31 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # untimed: time-based pre-warm, the W warm-up steps, then an all-kernel profile pass (per-layer table, and which §8d conv entry
-    # is the dominant one)
+    # untimed: time-based pre-warm, the W warm-up steps, then (--full) an all-kernel profile pass (per-layer table, and which §8d
+    # conv entry is the dominant one)
     prewarm_steps = prewarm(step, t.synchronize, args.prewarm_s, make_agree(torch, dist, dev, use_dist))
     for _ in range(max(args.warmup, 1)):
         step()
     t.synchronize()
-    t.profile_enable(True)
-    for _ in range(PROFILE_STEPS):
-        step()
-    t.synchronize()
-    prof_all = t.profile()
-    if args.dump_launch_order and rank == 0:
-        with open(args.dump_launch_order, "w") as f:
-            json.dump({"order": t.profile_launch_order()}, f, indent=0)
-    t.profile_reset()
-    layers, dims = layer_geometry(aa, cfg, TILE)
-    layer_rows, overhead = split_entries(prof_all, layers, dims, BATCH, PROFILE_STEPS)
-    dominant = max(layer_rows, key=lambda r: r["time_us"])["entry"] if layer_rows else ""
-    t.profile_set_filter(dominant)
-    # An event pair costs ~6 us of stream time per launch, so the timed region times the dominant entry on a sample of
-    # its steps (every 4th), not on all of them: the average launch duration is estimated from >= steps/4 launches.
-    sample_every = 4 if args.steps >= 8 else 1
-    t.profile_set_sampling(sample_every)
+    if args.full:
+        layers, dims = layer_geometry(aa, cfg, TILE)
+        t.profile_enable(True)
+        for _ in range(PROFILE_STEPS):
+            step()
+        t.synchronize()
+        prof_all = t.profile()
+        if args.dump_launch_order and rank == 0:
+            with open(args.dump_launch_order, "w") as f:
+                json.dump({"order": t.profile_launch_order()}, f, indent=0)
+        t.profile_reset()
+        layer_rows, overhead = split_entries(prof_all, layers, dims, BATCH, PROFILE_STEPS)
+        dominant = max(layer_rows, key=lambda r: r["time_us"])["entry"] if layer_rows else ""
+        t.profile_set_filter(dominant)
+        # An event pair costs ~6 us of stream time per launch, so the timed region times the dominant entry on a sample of
+        # its steps (every 4th), not on all of them: the average launch duration is estimated from >= steps/4 launches.
+        sample_every = 4 if args.steps >= 8 else 1
+        t.profile_set_sampling(sample_every)
+    restore_initial_state(t, initial_state)
 
     fence()
     t0 = time.perf_counter()
@@ -849,12 +918,14 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         elapsed = float(el.item())
     t.synchronize()
-    dom = [e for e in t.profile() if e["name"] == dominant]
+    dom = [e for e in t.profile() if e["name"] == dominant] if args.full else []
     loss = t.get_last_loss()
+    if args.dump_outputs and rank == 0:   # before the untimed extras below step the trainer on
+        dump_training_outputs(t, args.dump_outputs)
     # N > 1 (or launched as a rank): what ONE driver run must carry to be diagnosable — every rank's own step time, and the device time of
     # the exchange step measured by event pairs around each collective on four extra, untimed steps
     exchange = None
-    if use_dist:
+    if use_dist and args.full:
         mine = torch.tensor([1e3 * own_elapsed / args.steps], device=dev, dtype=torch.float64)
         per_rank = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(per_rank, mine)
@@ -878,7 +949,7 @@ def main():
     # pinned staging, uploads and runs the step behind the upload) — same step count, same instrumentation (event pairs on the dominant
     # entry, sampled).  PCIe-inclusive: reported beside `value`, never as it.  One process per GPU only (the N > 1 job feeds resident shards).
     elapsed_host = None
-    if world == 1 and not use_dist:
+    if world == 1 and not use_dist and args.full:
         import ctypes as C
         wl = [aa.set_weights(lab[i], 0.5, 0.5) for i in range(BATCH)]
         imgs = [np.ascontiguousarray(img[i]) for i in range(BATCH)]
@@ -898,6 +969,17 @@ def main():
     t.profile_enable(False)
 
     if rank == 0:
+        ms = 1e3 * elapsed / args.steps
+        out = {
+            "metric": "227x227 RGB tiles/sec fwd+bwd @ batch 32", "value": BATCH * world * args.steps / elapsed, "unit": "tiles/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "prewarm_s": args.prewarm_s if prewarm_steps else 0.0, "prewarm_steps": prewarm_steps, "ms_per_step": ms,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+            "config": {"workload": f"training step (fwd+loss+bwd+SGD), batch {BATCH}x3x{TILE}x{TILE} per GPU, encoder-decoder levels={LEVELS} width={WIDTH} K={CLASSES}, random init",
+                       "global_batch": BATCH * world, "parallelism": f"dp{world}"},
+            "ranks_seen": ranks_seen, "devices": devices,
+            "final_loss": loss,
+        }
+    if rank == 0 and args.full:
         roof = None
         if dom and dom[0]["launches"]:
             e = dom[0]
@@ -911,13 +993,7 @@ def main():
                         avg_launch_us=avg_s * 1e6, launches=e["launches"], sampled_every_n_steps=sample_every,
                         algorithmic_flops_per_launch=flops, algorithmic_bytes_per_launch=min_bytes, arithmetic_intensity=flops / min_bytes)
         step_gflop = 3 * sum(section8d(layers, dims, li, BATCH)[0] for li in range(len(layers))) / 1e9
-        ms = 1e3 * elapsed / args.steps
-        out = {
-            "metric": "227x227 RGB tiles/sec fwd+bwd @ batch 32", "value": BATCH * world * args.steps / elapsed, "unit": "tiles/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "prewarm_s": args.prewarm_s if prewarm_steps else 0.0, "prewarm_steps": prewarm_steps, "ms_per_step": ms,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
-            "config": {"workload": f"training step (fwd+loss+bwd+SGD), batch {BATCH}x3x{TILE}x{TILE} per GPU, encoder-decoder levels={LEVELS} width={WIDTH} K={CLASSES}, random init",
-                       "global_batch": BATCH * world, "parallelism": f"dp{world}"},
+        out.update({
             "value_host_inputs": None if elapsed_host is None else BATCH * args.steps / elapsed_host,
             "value_note": "value: the mini-batch resident in HBM when the timed region starts; value_host_inputs: the same K steps through anh_trainer_step with 32 host images + 32 host weighted-label images handed over every step (reference loop annonet_train_main.cpp:585-609; PCIe-inclusive, same step count and instrumentation)",
             "roofline": roof,
@@ -930,9 +1006,7 @@ def main():
             "layers_measured": f"HIP events on the launching stream, untimed profile pass of {PROFILE_STEPS} steps right before the timed region",
             "overhead_kernels": overhead,
             "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else cpu_baseline_train(aa, cfg),   # rank 0 at N=1 only
-            "ranks_seen": ranks_seen, "devices": devices,
-            "final_loss": loss,
-        }
+        })
         if os.environ.get("ANH_BENCH_VERBOSE"):
             for e in sorted(prof_all, key=lambda e: -e["total_ms"]):
                 per = e["total_ms"] / PROFILE_STEPS
@@ -947,9 +1021,9 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCPROFILER_") or k.startswith("ROCP_") for k in os.environ)
-        if not args.no_infer and not under_profiler:
+        if args.full and not args.no_infer and not under_profiler:
             out["infer"] = infer_in_child(args, world)
-        if world > 1 and not under_profiler and not args.no_in_process:
+        if args.full and world > 1 and not under_profiler and not args.no_in_process:
             out["in_process"] = in_process_child(args, world)   # host (B): the same N GPUs from ONE process (anh_set_devices)
         print(json.dumps(out), flush=True)
 

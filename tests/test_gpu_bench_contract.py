@@ -1,5 +1,6 @@
-"""bench.py's one-line contract (the driver parses it): metric / value / unit / step counts, the roofline object of the
-dominant kernel measured live, the CPU baseline of the same run, and the fields that must NOT claim more than was measured.
+"""bench.py's one-line contract (the driver parses it): metric / value / unit / step counts, and with --full the roofline object
+of the dominant kernel measured live, the CPU baseline of the same run, and the fields that must NOT claim more than was measured;
+a plain run's lean line and the outputs --dump-outputs writes.
 These tests check the SHAPE of the line (fields, units, consistency between fields) — never a rate: a wall-clock bound in a
 test is noise on a shared box, and under -x it would hide every test collected after it (tests/conftest.py runs this file last)."""
 import json
@@ -7,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +25,7 @@ def run_bench(*args):
 
 
 def test_training_bench_line():
-    d = run_bench("--gpus", "1", "--steps", "8", "--warmup", "2", "--prewarm-s", "0.5", "--infer-steps", "2")
+    d = run_bench("--gpus", "1", "--steps", "8", "--warmup", "2", "--prewarm-s", "0.5", "--infer-steps", "2", "--full")
     assert d["metric"].startswith("227x227 RGB tiles/sec fwd+bwd") and d["unit"] == "tiles/s"
     assert d["n_gpus"] == 1 and d["steps"] == 8 and d["warmup"] == 2 and d["higher_is_better"] is True
     assert d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "bf16" and d["data"] == "synthetic"
@@ -68,6 +70,41 @@ def test_training_bench_line():
     assert [o["metric"].split(",")[1].strip() for o in i["other_sizes"]] == ["16384x16384 image"]
 
 
+# what only --full measures: none of it may appear in (or slow down) a plain run
+FULL_ONLY = ("roofline", "layers", "overhead_kernels", "critical_path", "step_roofline", "cpu_baseline", "value_host_inputs", "exchange", "infer",
+             "in_process", "value_labels_on_host", "kernel_time_share_pct")
+
+
+def test_plain_training_line_and_its_outputs(tmp_path):
+    """A plain run: set-up, pre-warm, warm-up, exactly --steps timed steps, the headline fields.  --dump-outputs writes what the
+    last timed step computed; the timed steps start from the trainer's initial state, so a different pre-warm gives the same
+    outputs bit for bit."""
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = run_bench("--gpus", "1", "--steps", "6", "--warmup", "2", "--prewarm-s", "0.3", "--dump-outputs", str(a))
+    assert d["metric"].startswith("227x227 RGB tiles/sec fwd+bwd") and d["unit"] == "tiles/s" and d["higher_is_better"] is True
+    assert d["steps"] == 6 and d["warmup"] == 2 and d["dtype"] == "bf16" and d["n_gpus"] == 1 and d["prewarm_steps"] >= 4
+    assert d["value"] > 0 and abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert not set(FULL_ONLY) & set(d), sorted(set(FULL_ONLY) & set(d))
+    params, running, loss = (np.load(a / f"{n}.npy") for n in ("params", "running_stats", "loss"))
+    assert params.dtype == np.float32 and params.shape == (418435,) and running.dtype == np.float32 and running.size > 0
+    assert loss.dtype == np.float64 and loss.shape == (1,) and loss[0] == d["final_loss"]
+    assert np.isfinite(params).all() and np.isfinite(running).all() and np.isfinite(loss).all()
+    d2 = run_bench("--gpus", "1", "--steps", "6", "--warmup", "2", "--prewarm-s", "0", "--dump-outputs", str(b))
+    assert d2["prewarm_steps"] == 0 and d2["final_loss"] == d["final_loss"]
+    for n in ("params", "running_stats", "loss"):
+        np.testing.assert_array_equal(np.load(b / f"{n}.npy"), np.load(a / f"{n}.npy"), err_msg=n)
+
+
+def test_plain_inference_line_and_its_outputs(tmp_path):
+    """--mode infer without --full: --steps / --warmup as given (no mode default overrides them), the lean line, the label map."""
+    d = run_bench("--mode", "infer", "--image-side", "300", "--steps", "200", "--warmup", "1", "--prewarm-s", "0", "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 200 and d["warmup"] == 1 and d["unit"] == "Mpx/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["value"] > 0 and abs(d["value"] - 300 * 300 / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-6 * d["value"]
+    assert not set(FULL_ONLY) & set(d), sorted(set(FULL_ONLY) & set(d))
+    labels = np.load(tmp_path / "labels.npy")
+    assert labels.dtype == np.float32 and labels.shape == (300 * 300,) and set(np.unique(labels)) <= {0.0, 1.0, 2.0}
+
+
 def test_self_launch_refuses_more_gpus_than_visible():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "64", "--steps", "1", "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 2 and "GPU(s) visible" in r.stderr
@@ -85,7 +122,7 @@ def test_launched_as_a_rank_takes_the_rccl_path():
 
 
 def test_inference_bench_line():
-    d = run_bench("--mode", "infer", "--image-side", "2048", "--steps", "3", "--warmup", "1", "--prewarm-s", "0.2")
+    d = run_bench("--mode", "infer", "--image-side", "2048", "--steps", "3", "--warmup", "1", "--prewarm-s", "0.2", "--full")
     assert d["unit"] == "Mpx/s" and d["n_gpus"] == 1 and d["scaling"] == "strong" and d["vs_baseline"] is None
     assert d["config"]["exchanged_pixels"] == 0 and d["value"] > 0 and d["value_labels_on_host"] > 0 and d["steps"] == 3
     r = d["roofline"]
@@ -96,7 +133,7 @@ def test_inference_bench_line():
 
 
 def test_fp32_inference_entries_name_the_matrix_kernels():
-    d = run_bench("--mode", "infer", "--image-side", "1024", "--steps", "1", "--warmup", "1", "--prewarm-s", "0", "--precision", "fp32", "--no-cpu-baseline")
+    d = run_bench("--mode", "infer", "--image-side", "1024", "--steps", "1", "--warmup", "1", "--prewarm-s", "0", "--precision", "fp32", "--no-cpu-baseline", "--full")
     assert d["roofline"]["kernel"].startswith("conv_mfma_f32:fwd_L")     # the fp32 parity mode runs on v_mfma_f32_32x32x2_f32, and says so
 
 
@@ -105,7 +142,7 @@ def test_two_rank_job_rehearsed_on_one_gpu():
     (dist.EarlyReduce), the agreed pre-warm, and in the inference child the overlap exchange and the label gather — with both ranks on
     device 0 and gloo as the transport (RCCL wants one GPU per rank; the one-GPU test box cannot run it at world size 2)."""
     d = run_bench("--gpus", "2", "--backend", "gloo", "--one-gpu", "--steps", "3", "--warmup", "1", "--prewarm-s", "0.3", "--no-cpu-baseline",
-                  "--infer-steps", "2", "--infer-sides", "2048")
+                  "--infer-steps", "2", "--infer-sides", "2048", "--full")
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["devices"] == [0, 0] and d["config"]["global_batch"] == 64
     assert d["value"] > 0 and abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]      # whole-job tiles per second
     assert d["cpu_baseline"] is None and d["scaling"] == "weak" and d["prewarm_steps"] >= 4
