@@ -697,7 +697,10 @@ namespace {
 // into planes of its own, ONE all-reduce sums the planes inside the rectangles where tiles of different replicas overlap
 // (strips one receptive field wide), every replica labels the rows its tiles cover, and the host label map is assembled tile
 // by tile from the owner of each tile (in an overlap both owners hold the same sums, hence the same labels).
-void infer_multi(anh_runtime* h, const uint8_t* image, int H, int W, const double* gains, const std::vector<anh_tile>& tiles, uint16_t* result, float* blended_out) {
+// `original` (anh_infer_scaled): the image comes at its original size OH x OW; every replica uploads it and shrinks it to H x W itself
+// (the shrunk image is integer-valued and identical everywhere), `image` is unused.
+void infer_multi(anh_runtime* h, const uint8_t* image, int H, int W, const double* gains, const std::vector<anh_tile>& tiles, uint16_t* result, float* blended_out,
+                 const uint8_t* original = nullptr, int OH = 0, int OW = 0) {
     const size_t R = h->replicas();
     const int K = h->eng->spec.cfg.classes, C = h->eng->spec.cfg.in_channels;
     const size_t plane = (size_t)H * W;
@@ -713,7 +716,12 @@ void infer_multi(anh_runtime* h, const uint8_t* image, int H, int W, const doubl
         e.stage_image.reserve(plane * C);
         e.stage_blended.reserve(plane * K * 4);
         e.stage_result.reserve(plane * 2);
-        HIP_CHECK(hipMemcpyAsync(e.stage_image.p, image, plane * C, hipMemcpyHostToDevice, e.stream));
+        if (original) {
+            e.stage_original.reserve((size_t)OH * OW * C);
+            HIP_CHECK(hipMemcpyAsync(e.stage_original.p, original, (size_t)OH * OW * C, hipMemcpyHostToDevice, e.stream));
+            e.resize_image(e.stage_original.as<uint8_t>(), OH, OW, e.stage_image.as<uint8_t>(), H, W);
+        } else
+            HIP_CHECK(hipMemcpyAsync(e.stage_image.p, image, plane * C, hipMemcpyHostToDevice, e.stream));
         const std::vector<anh_tile> mine(tiles.begin() + lo[r], tiles.begin() + hi[r]);
         e.infer_device(e.stage_image.as<uint8_t>(), H, W, gains, mine, nullptr, e.stage_blended.as<float>());
         streams[r] = e.stream;
@@ -793,6 +801,127 @@ int anh_infer(anh_runtime* h, const uint8_t* image, int height, int width, const
             run_detection_filter(e.stage_blended.as<float>(), e.stage_result.as<uint16_t>(), K, height, width, d_det, flags, d_changed, e.stream);
         }
         HIP_CHECK(hipMemcpyAsync(result, e.stage_result.p, plane * 2, hipMemcpyDeviceToHost, e.stream));
+        if (blended_out) HIP_CHECK(hipMemcpyAsync(blended_out, e.stage_blended.p, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
+        e.synchronize();
+    });
+}
+
+// ---- downscaled inference: read_sample's resize (annonet.cpp:153) + annonet_infer() + resize_label_image (annonet.cpp:132-141) ----
+namespace {
+// std::round(size_scale * side) with size_scale = 1.0 / factor: the expression of annonet_host.h's resize_image_bilinear, which is
+// dlib::resize_image(1.0 / factor, img) as read_sample calls it
+void scaled_dims_checked(int height, int width, double factor, int& sh, int& sw) {
+    ANH_REQUIRE(height >= 1 && width >= 1, "empty image");
+    ANH_REQUIRE(std::isfinite(factor) && factor > 0.0, "the downscaling factor must be a positive finite number");
+    const double scale = 1.0 / factor;
+    const double nr = std::round(scale * height), nc = std::round(scale * width);
+    ANH_REQUIRE(nr >= 1 && nc >= 1, "the image is too small for this downscaling factor: a scaled side would be below 1 pixel");
+    ANH_REQUIRE(nr <= 32768 && nc <= 32768, "the downscaling factor enlarges the image beyond 32768 pixels per side");
+    sh = (int)nr; sw = (int)nc;
+}
+}  // namespace
+
+int anh_scaled_dims(int height, int width, double downscaling_factor, int* scaled_height, int* scaled_width) {
+    return guarded([&] {
+        ANH_REQUIRE(scaled_height && scaled_width, "null argument");
+        scaled_dims_checked(height, width, downscaling_factor, *scaled_height, *scaled_width);
+    });
+}
+
+int anh_resize_image_device(const uint8_t* d_src, int channels, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w, void* hip_stream) {
+    return guarded([&] {
+        ANH_REQUIRE(d_src && d_dst, "null argument");
+        ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1 && src_h <= 32768 && src_w <= 32768 && dst_h <= 32768 && dst_w <= 32768, "resize_image: sides must be within 1..32768");
+        launch_resize_image_bilinear(d_src, channels, src_h, src_w, d_dst, dst_h, dst_w, (hipStream_t)hip_stream);
+    });
+}
+
+int anh_resize_labels_device(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w, void* hip_stream) {
+    return guarded([&] {
+        ANH_REQUIRE(d_src && d_dst, "null argument");
+        ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1 && src_h <= 32768 && src_w <= 32768 && dst_h <= 32768 && dst_w <= 32768, "resize_labels: sides must be within 1..32768");
+        launch_resize_labels_nearest(d_src, src_h, src_w, d_dst, dst_h, dst_w, (hipStream_t)hip_stream);
+    });
+}
+
+int anh_infer_scaled_device(anh_runtime* h, const uint8_t* d_image, int height, int width, double downscaling_factor, const double* gains,
+                            const anh_tiling_params* tiling, uint16_t* d_result, uint16_t* d_scaled_labels, float* d_blended) {
+    return guarded([&] {
+        ANH_REQUIRE(h && d_image && d_result, "null argument");
+        int sh = 0, sw = 0;
+        scaled_dims_checked(height, width, downscaling_factor, sh, sw);
+        DeviceScope scope(h->device_of(0));
+        Engine& e = *h->eng;
+        const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
+        const size_t plane = (size_t)sh * sw;
+        const std::vector<anh_tile> tiles = tiles_for(tiling, sw, sh);
+        if (!d_blended) { e.stage_blended.reserve(plane * K * 4); d_blended = e.stage_blended.as<float>(); }
+        if (downscaling_factor == 1.0) {   // the host's bilinear returns early at scale 1, nearest neighbour at equal size is the identity
+            e.infer_device(d_image, height, width, gains, tiles, d_result, d_blended, /*whole_image=*/true);
+            if (d_scaled_labels) HIP_CHECK(hipMemcpyAsync(d_scaled_labels, d_result, plane * 2, hipMemcpyDeviceToDevice, e.stream));
+            return;
+        }
+        e.stage_image.reserve(plane * C);
+        if (!d_scaled_labels) { e.stage_result.reserve(plane * 2); d_scaled_labels = e.stage_result.as<uint16_t>(); }
+        e.resize_image(d_image, height, width, e.stage_image.as<uint8_t>(), sh, sw);
+        e.infer_device(e.stage_image.as<uint8_t>(), sh, sw, gains, tiles, d_scaled_labels, d_blended, /*whole_image=*/true);
+        e.resize_labels(d_scaled_labels, sh, sw, d_result, height, width);
+    });
+}
+
+int anh_infer_scaled(anh_runtime* h, const uint8_t* image, int height, int width, double downscaling_factor, const double* gains,
+                     const double* detection_levels, const anh_tiling_params* tiling, uint16_t* result, uint16_t* scaled_labels, float* blended_out) {
+    return guarded([&] {
+        ANH_REQUIRE(h && image && result, "null argument");
+        int sh = 0, sw = 0;
+        scaled_dims_checked(height, width, downscaling_factor, sh, sw);
+        const size_t plane = (size_t)sh * sw, full = (size_t)height * width;
+        if (downscaling_factor == 1.0) {   // exactly anh_infer: the host's bilinear returns early at scale 1, nearest neighbour at equal size is the identity
+            const int rc = anh_infer(h, image, height, width, gains, detection_levels, tiling, result, blended_out);
+            if (rc != ANH_OK) fail(rc, g_error);
+            if (scaled_labels) std::memcpy(scaled_labels, result, full * 2);
+            return;
+        }
+        DeviceScope scope(h->device_of(0));
+        Engine& e = *h->eng;
+        const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
+        const std::vector<anh_tile> tiles = tiles_for(tiling, sw, sh);
+        bool use_det = false;
+        if (detection_levels) for (int k = 0; k < K; ++k) { ANH_REQUIRE(detection_levels[k] >= 0.0, "detection levels must be >= 0"); if (detection_levels[k] > 0.0) use_det = true; }
+        e.stage_original.reserve(full * C);
+        e.stage_image.reserve(plane * C);
+        e.stage_blended.reserve(plane * K * 4);
+        e.stage_result.reserve(plane * 2);
+        e.stage_upsampled.reserve(full * 2);
+        if (h->replicas() > 1 && !use_det && tiles.size() >= 2) {
+            // the sharded path (infer_multi): every replica shrinks the image itself; the merged map is assembled on the host from the
+            // owners of its tiles, as for anh_infer, and replica 0 blows it up
+            std::vector<uint16_t> merged_own;
+            uint16_t* merged = scaled_labels;
+            if (!merged) { merged_own.resize(plane); merged = merged_own.data(); }
+            infer_multi(h, nullptr, sh, sw, gains, tiles, merged, blended_out, image, height, width);
+            HIP_CHECK(hipMemcpyAsync(e.stage_result.p, merged, plane * 2, hipMemcpyHostToDevice, e.stream));
+            e.resize_labels(e.stage_result.as<uint16_t>(), sh, sw, e.stage_upsampled.as<uint16_t>(), height, width);
+            HIP_CHECK(hipMemcpyAsync(result, e.stage_upsampled.p, full * 2, hipMemcpyDeviceToHost, e.stream));
+            e.synchronize();
+            return;
+        }
+        // one stream: original image up, shrink, tiles, (detection-level filter at the net's resolution, as the reference runs it before
+        // resize_label_image), blow the map up, original-size map down
+        HIP_CHECK(hipMemcpyAsync(e.stage_original.p, image, full * C, hipMemcpyHostToDevice, e.stream));
+        e.resize_image(e.stage_original.as<uint8_t>(), height, width, e.stage_image.as<uint8_t>(), sh, sw);
+        e.infer_device(e.stage_image.as<uint8_t>(), sh, sw, gains, tiles, e.stage_result.as<uint16_t>(), e.stage_blended.as<float>(), /*whole_image=*/true);
+        if (use_det) {
+            e.stage_out.reserve(plane + (size_t)K * sizeof(double) + 64);
+            uint8_t* flags = e.stage_out.as<uint8_t>();
+            double* d_det = reinterpret_cast<double*>(flags + ((plane + 15) / 16) * 16);
+            int* d_changed = reinterpret_cast<int*>(d_det + K);
+            HIP_CHECK(hipMemcpyAsync(d_det, detection_levels, (size_t)K * sizeof(double), hipMemcpyHostToDevice, e.stream));
+            run_detection_filter(e.stage_blended.as<float>(), e.stage_result.as<uint16_t>(), K, sh, sw, d_det, flags, d_changed, e.stream);
+        }
+        e.resize_labels(e.stage_result.as<uint16_t>(), sh, sw, e.stage_upsampled.as<uint16_t>(), height, width);
+        HIP_CHECK(hipMemcpyAsync(result, e.stage_upsampled.p, full * 2, hipMemcpyDeviceToHost, e.stream));
+        if (scaled_labels) HIP_CHECK(hipMemcpyAsync(scaled_labels, e.stage_result.p, plane * 2, hipMemcpyDeviceToHost, e.stream));
         if (blended_out) HIP_CHECK(hipMemcpyAsync(blended_out, e.stage_blended.p, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
         e.synchronize();
     });

@@ -140,6 +140,13 @@ class Engine {
 
     // scratch exposed to the C ABI layer (host-pointer entry points stage through these)
     DevBuf stage_image, stage_labels, stage_weights, stage_out, stage_blended, stage_result;
+    // downscaled inference (anh_infer_scaled): the image at its original size, and the label map blown back up to it.  Buffers of their
+    // own: the inference pass in between reads stage_image and writes stage_blended / stage_result.
+    DevBuf stage_original, stage_upsampled;
+    // read_sample's resize + annonet_infer() + resize_label_image on resident buffers: d_original [H][W][C] -> d_scaled_image
+    // [sh][sw][C] -> tiles -> d_scaled_labels [sh][sw] (and d_blended [K][sh][sw]) -> d_labels [H][W]
+    void resize_image(const uint8_t* d_src, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w);
+    void resize_labels(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w);
     std::vector<float> host_out;
 
   private:

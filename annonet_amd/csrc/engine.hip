@@ -1102,4 +1102,17 @@ void Engine::argmax_rows(const float* d_blended, int H, int W, int row0, int row
     prof.end(stream, tok);
 }
 
+void Engine::resize_image(const uint8_t* d_src, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w) {
+    const int C = spec.cfg.in_channels;
+    const int tok = prof.begin(stream, "resize_image_bilinear", 0, ((double)src_h * src_w + (double)dst_h * dst_w) * C);
+    launch_resize_image_bilinear(d_src, C, src_h, src_w, d_dst, dst_h, dst_w, stream);
+    prof.end(stream, tok);
+}
+
+void Engine::resize_labels(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w) {
+    const int tok = prof.begin(stream, "resize_labels_nearest", 0, ((double)src_h * src_w + (double)dst_h * dst_w) * 2.0);
+    launch_resize_labels_nearest(d_src, src_h, src_w, d_dst, dst_h, dst_w, stream);
+    prof.end(stream, tok);
+}
+
 }  // namespace anh

@@ -240,6 +240,12 @@ void launch_argmax_range(const float* blended, int k, int64_t pixels, int64_t p0
 void launch_fill_zero(void* p, size_t bytes, hipStream_t s);
 void launch_zero_rects(float* planes, int k, int H, int W, const anh_rect* d_rects, int n, hipStream_t s);   // zero n inclusive rectangles of every plane [k][H][W]
 
+// Whole-image resizes of downscaled inference, with the arithmetic of annonet_host.h (resize_image_bilinear, resize_label_image):
+// u8 HWC image (1 or 3 channels) -> bilinear on dlib::resize_image's corner-aligned grid; u16 label map -> nearest neighbour.
+// Any source and destination size; every destination element is written.
+void launch_resize_image_bilinear(const uint8_t* d_src, int channels, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w, hipStream_t s);
+void launch_resize_labels_nearest(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w, hipStream_t s);
+
 // Training crops cut on the device from full images resident in HBM (randomly_crop_image, annonet_train_main.cpp:110-232,
 // for further_downscaling_factor = 1 and given draws).  kCropMaxClasses bounds the label values the histogram covers.
 constexpr int kCropMaxClasses = 64;

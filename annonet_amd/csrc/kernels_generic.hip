@@ -2341,4 +2341,122 @@ void launch_fill_zero(void* p, size_t bytes, hipStream_t s) {
     HIP_CHECK(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------------------------------
+// whole-image resizes of downscaled inference (read_sample's resize_image, annonet.cpp:153; resize_label_image, annonet.cpp:132-141)
+// ---------------------------------------------------------------------------------------------------
+// dlib::resize_image's corner-aligned grid [UPSTREAM-UNVERIFIED], exactly as annonet_host.h restates it (resize_image_bilinear):
+// coordinates in double, the fractions and the interpolation in float, rounded half up.  The arithmetic is the host's expression tree
+// evaluated operation by operation: it is bit-exact only because the build compiles with -ffp-contract=off (no fused multiply-add).
+//
+// A work item is (output row, chunk of 256 units); a unit is what one lane writes: kResizeImagePixels consecutive output pixels
+// (4 or 12 bytes) that start on a dword boundary of the destination, so a full unit leaves as 1 or 3 dword stores.  Rows start at any
+// byte address (width * channels is arbitrary): the first `head` pixels of a row (0..3) and the last few go out as bytes.
+constexpr int kResizeImagePixels = 4;
+template <int C>
+__global__ __launch_bounds__(256) void resize_image_bilinear_kernel(const uint8_t* __restrict__ src, int in_nr, int in_nc, uint8_t* __restrict__ dst, int out_nr, int out_nc,
+                                                                     int chunks, int64_t items) {
+    const double x_scale = (in_nc - 1) / (double)max(out_nc - 1, 1), y_scale = (in_nr - 1) / (double)max(out_nr - 1, 1);
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int r = (int)(item / chunks), chunk = (int)(item - (int64_t)r * chunks);
+        // per-row quantities, once per work item
+        const double y = r * y_scale;
+        const int top = min(max((int)floor(y), 0), in_nr - 1), bottom = min(top + 1, in_nr - 1);
+        const float fy = (float)(y - top);
+        const uint8_t* row_t = src + (int64_t)top * in_nc * C;
+        const uint8_t* row_b = src + (int64_t)bottom * in_nc * C;
+        uint8_t* out_row = dst + (int64_t)r * out_nc * C;
+        const int a = (int)(reinterpret_cast<uintptr_t>(out_row) & 3);
+        const int head = C == 3 ? a : (4 - a) & 3;   // pixels before the first dword boundary that is also a pixel boundary (3 * head = -a mod 4)
+        const int unit = chunk * 256 + (int)threadIdx.x;   // unit 0 = the head pixels, unit u >= 1 = pixels [head + 4 (u - 1), head + 4 u)
+        const int c0 = unit == 0 ? 0 : head + kResizeImagePixels * (unit - 1), c1 = min(out_nc, head + kResizeImagePixels * unit);
+        if (c0 >= c1) continue;
+        uint8_t v[kResizeImagePixels * C];
+        for (int i = 0; i < kResizeImagePixels; ++i) {
+            const int c = min(c0 + i, out_nc - 1);   // lanes of a partial unit compute a valid column twice and store less
+            const double x = c * x_scale;
+            const int left = min(max((int)floor(x), 0), in_nc - 1), right = min(left + 1, in_nc - 1);
+            const float fx = (float)(x - left);
+            for (int ch = 0; ch < C; ++ch) {
+                const float tl = row_t[(int64_t)left * C + ch], tr = row_t[(int64_t)right * C + ch];
+                const float bl = row_b[(int64_t)left * C + ch], br = row_b[(int64_t)right * C + ch];
+                const float val = (1 - fy) * ((1 - fx) * tl + fx * tr) + fy * ((1 - fx) * bl + fx * br);
+                v[i * C + ch] = (uint8_t)(val + 0.5f);
+            }
+        }
+        uint8_t* o = out_row + (int64_t)c0 * C;
+        if (unit != 0 && c1 - c0 == kResizeImagePixels) {
+            uint32_t* o32 = reinterpret_cast<uint32_t*>(o);
+            for (int w = 0; w < C; ++w)
+                o32[w] = (uint32_t)v[4 * w] | ((uint32_t)v[4 * w + 1] << 8) | ((uint32_t)v[4 * w + 2] << 16) | ((uint32_t)v[4 * w + 3] << 24);
+        } else {
+            const int n = (c1 - c0) * C;
+#pragma unroll
+            for (int i = 0; i < kResizeImagePixels * C; ++i) if (i < n) o[i] = v[i];
+        }
+    }
+}
+
+void launch_resize_image_bilinear(const uint8_t* d_src, int channels, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w, hipStream_t s) {
+    ANH_REQUIRE(channels == 1 || channels == 3, "resize_image: 1 or 3 channels");
+    ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1, "resize_image: empty image");
+    const int units = 1 + (dst_w + kResizeImagePixels - 1) / kResizeImagePixels + 1;   // head unit + full units (+1: a head shifts the last one)
+    const int chunks = (units + 255) / 256;
+    const int64_t items = (int64_t)dst_h * chunks;
+    const int blocks = (int)std::min<int64_t>(items, 256 * 16);   // bounded grid-stride: at most 16 workgroups per CU
+    if (channels == 3) hipLaunchKernelGGL(resize_image_bilinear_kernel<3>, dim3(blocks), dim3(256), 0, s, d_src, src_h, src_w, d_dst, dst_h, dst_w, chunks, items);
+    else hipLaunchKernelGGL(resize_image_bilinear_kernel<1>, dim3(blocks), dim3(256), 0, s, d_src, src_h, src_w, d_dst, dst_h, dst_w, chunks, items);
+    HIP_CHECK(hipGetLastError());
+}
+
+// dlib::resize_image + interpolate_nearest_neighbor [UPSTREAM-UNVERIFIED], as annonet_host.h restates it (resize_label_image): the source
+// column of output column c is floor(c * x_scale + 0.5) in double, the same for rows.  The output is the large side (the original-size
+// map), so it leaves as 16-byte stores of eight labels; the source is 1/factor^2 of it and is re-read from cache.
+//
+// A work item is (band of kResizeLabelRows output rows, chunk of 256 * 8 output columns).  The workgroup computes the source columns of
+// its chunk once, into LDS, and then walks the rows of the band.  A lane owns eight consecutive labels that start on a 16-byte boundary
+// of the destination; where a row starts between boundaries (odd widths), its lanes shift left by `back` labels (0..7), which is why the
+// table starts seven columns before the chunk.  Partial units (row ends) go out label by label.
+constexpr int kResizeLabelRows = 32, kResizeLabelCols = 256 * 8;
+__global__ __launch_bounds__(256) void resize_labels_nearest_kernel(const uint16_t* __restrict__ src, int in_nr, int in_nc, uint16_t* __restrict__ dst, int out_nr, int out_nc,
+                                                                     int chunks, int64_t items) {
+    __shared__ int sx[kResizeLabelCols + 8];
+    const double x_scale = (in_nc - 1) / (double)max(out_nc - 1, 1), y_scale = (in_nr - 1) / (double)max(out_nr - 1, 1);
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int band = (int)(item / chunks), chunk = (int)(item - (int64_t)band * chunks);
+        const int col0 = chunk * kResizeLabelCols - 7;   // column of sx[0]
+        __syncthreads();   // the previous item's rows are done with the table
+        for (int j = threadIdx.x; j < kResizeLabelCols + 7; j += 256) {
+            const int c = min(max(col0 + j, 0), out_nc - 1);
+            sx[j] = min(max((int)floor(c * x_scale + 0.5), 0), in_nc - 1);
+        }
+        __syncthreads();
+        const int r_end = min(out_nr, (band + 1) * kResizeLabelRows);
+        for (int r = band * kResizeLabelRows; r < r_end; ++r) {
+            const int sy = min(max((int)floor(r * y_scale + 0.5), 0), in_nr - 1);
+            const uint16_t* in_row = src + (int64_t)sy * in_nc;
+            uint16_t* out_row = dst + (int64_t)r * out_nc;
+            const int back = (int)((reinterpret_cast<uintptr_t>(out_row) & 15) >> 1);   // labels between the previous 16-byte boundary and the row start
+            const int j0 = 7 + 8 * (int)threadIdx.x - back;                             // table index of this lane's first label
+            const int c0 = col0 + j0;                                                   // = chunk * 2048 + 8 * lane - back
+            if (c0 >= 0 && c0 + 8 <= out_nc) {
+                uint32_t w[4];
+                for (int i = 0; i < 4; ++i) w[i] = (uint32_t)in_row[sx[j0 + 2 * i]] | ((uint32_t)in_row[sx[j0 + 2 * i + 1]] << 16);
+                *reinterpret_cast<uint4*>(out_row + c0) = make_uint4(w[0], w[1], w[2], w[3]);
+            } else {
+                for (int i = 0; i < 8; ++i) { const int c = c0 + i; if (c >= 0 && c < out_nc) out_row[c] = in_row[sx[j0 + i]]; }
+            }
+        }
+    }
+}
+
+void launch_resize_labels_nearest(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w, hipStream_t s) {
+    ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1, "resize_labels: empty label image");
+    ANH_REQUIRE((reinterpret_cast<uintptr_t>(d_dst) & 1) == 0 && (reinterpret_cast<uintptr_t>(d_src) & 1) == 0, "resize_labels: label maps must be 2-byte aligned");
+    const int chunks = (dst_w + 7 + kResizeLabelCols - 1) / kResizeLabelCols;   // + 7: the shift of a row that starts off a 16-byte boundary
+    const int64_t items = (int64_t)((dst_h + kResizeLabelRows - 1) / kResizeLabelRows) * chunks;
+    const int blocks = (int)std::min<int64_t>(items, 256 * 16);
+    hipLaunchKernelGGL(resize_labels_nearest_kernel, dim3(blocks), dim3(256), 0, s, d_src, src_h, src_w, d_dst, dst_h, dst_w, chunks, items);
+    HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace anh

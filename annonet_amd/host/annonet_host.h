@@ -245,16 +245,9 @@ void resize_label_image(image_type& label_image, int target_width, int target_he
 
 // dlib::resize_image(size_scale, img) with the default bilinear interpolation [UPSTREAM-UNVERIFIED]: new size = round(scale * old),
 // same corner-aligned sampling grid as above, channels interpolated in float and rounded half up.  Scale 1 is the identity.
-inline void resize_image_bilinear(double size_scale, NetPimpl::input_type& img) {
-    if (size_scale == 1.0) return;
-    const long in_nr = img.nr(), in_nc = img.nc();
-    const long out_nr = (long)std::round(size_scale * in_nr), out_nc = (long)std::round(size_scale * in_nc);
-    if (out_nr < 1 || out_nc < 1) throw std::runtime_error("image is too small for this downscaling factor");
-    NetPimpl::input_type out;
-    out.set_size(out_nr, out_nc);
-    constexpr int C = NetPimpl::kInputChannels;
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(&*img.begin());
-    uint8_t* dst = reinterpret_cast<uint8_t*>(&*out.begin());
+// The sampling itself, on raw u8 HWC pixels with C interleaved channels (host_selftest's resize-image checks it for 1 and 3 channels;
+// the device's resize_image_bilinear_kernel repeats this arithmetic operation by operation).
+inline void resize_bilinear_u8(const uint8_t* src, long in_nr, long in_nc, int C, uint8_t* dst, long out_nr, long out_nc) {
     const double x_scale = (in_nc - 1) / (double)std::max<long>(out_nc - 1, 1), y_scale = (in_nr - 1) / (double)std::max<long>(out_nr - 1, 1);
     for (long r = 0; r < out_nr; ++r) {
         const double y = r * y_scale;
@@ -272,6 +265,15 @@ inline void resize_image_bilinear(double size_scale, NetPimpl::input_type& img) 
             }
         }
     }
+}
+inline void resize_image_bilinear(double size_scale, NetPimpl::input_type& img) {
+    if (size_scale == 1.0) return;
+    const long in_nr = img.nr(), in_nc = img.nc();
+    const long out_nr = (long)std::round(size_scale * in_nr), out_nc = (long)std::round(size_scale * in_nc);
+    if (out_nr < 1 || out_nc < 1) throw std::runtime_error("image is too small for this downscaling factor");
+    NetPimpl::input_type out;
+    out.set_size(out_nr, out_nc);
+    resize_bilinear_u8(reinterpret_cast<const uint8_t*>(&*img.begin()), in_nr, in_nc, NetPimpl::kInputChannels, reinterpret_cast<uint8_t*>(&*out.begin()), out_nr, out_nc);
     std::swap(img, out);
 }
 
@@ -310,7 +312,10 @@ inline void save_png(const dlib::matrix<dlib::rgb_alpha_pixel>& image, const std
     annonet_io::save_raster_png(r, filename);
 }
 
-inline sample_type read_sample(const image_filenames_type& image_filenames, const std::vector<AnnoClass>& anno_classes, bool require_ground_truth, double downscaling_factor) {   // annonet.cpp:143-176
+// resize_input_image = false (the inference program when annonet_infer_scaled shrinks the image on the GPU): the image stays at its
+// original size; the ground truth is still brought to the size the shrunk image WOULD have (anh_scaled_dims), where it is scored.
+inline sample_type read_sample(const image_filenames_type& image_filenames, const std::vector<AnnoClass>& anno_classes, bool require_ground_truth, double downscaling_factor,
+                               bool resize_input_image = true) {   // annonet.cpp:143-176
     sample_type sample;
     sample.image_filenames = image_filenames;
     try {
@@ -318,12 +323,16 @@ inline sample_type read_sample(const image_filenames_type& image_filenames, cons
         load_input_image(sample.input_image, image_filenames.image_filename);
         sample.original_width = (int)sample.input_image.nc();
         sample.original_height = (int)sample.input_image.nr();
-        resize_image_bilinear(1.0 / downscaling_factor, sample.input_image);
+        int scaled_height = sample.original_height, scaled_width = sample.original_width;
+        if (resize_input_image) {
+            resize_image_bilinear(1.0 / downscaling_factor, sample.input_image);
+            scaled_height = (int)sample.input_image.nr(); scaled_width = (int)sample.input_image.nc();
+        } else if (downscaling_factor != 1.0) NetPimpl::check(anh_scaled_dims(sample.original_height, sample.original_width, downscaling_factor, &scaled_height, &scaled_width));
         if (!image_filenames.label_filename.empty()) {
             load_rgba_image(rgba_label_image, image_filenames.label_filename);
             if (rgba_label_image.nr() != sample.original_height || rgba_label_image.nc() != sample.original_width) sample.error = "Label image size mismatch";
             else {
-                resize_label_image(rgba_label_image, (int)sample.input_image.nc(), (int)sample.input_image.nr());
+                resize_label_image(rgba_label_image, scaled_width, scaled_height);
                 decode_rgba_label_image(rgba_label_image, sample, anno_classes);
             }
         } else if (require_ground_truth) sample.error = "No ground truth available";

@@ -21,7 +21,7 @@ static void print_matrix(const ConfusionMatrix& m) {
 
 int main(int argc, char** argv) try {
     const std::vector<std::string> a(argv + 1, argv + argc);
-    if (a.empty()) throw std::runtime_error("usage: host_selftest <png-roundtrip|classes|decode-mask|resize-labels|confusion|print-confusion> ...");
+    if (a.empty()) throw std::runtime_error("usage: host_selftest <png-roundtrip|classes|decode-mask|resize-labels|resize-image|confusion|print-confusion> ...");
     if (a[0] == "png-roundtrip") {   // in out: decode -> encode (what load_image / save_png do)
         annonet_io::save_raster_png(annonet_io::load_raster(a.at(1)), a.at(2));
     } else if (a[0] == "classes") {   // json-file ("-" = the empty string): index r g b a name
@@ -41,6 +41,22 @@ int main(int argc, char** argv) try {
         auto m = read_u16(a.at(1), std::stol(a.at(2)), std::stol(a.at(3)));
         resize_label_image(m, std::stoi(a.at(4)), std::stoi(a.at(5)));
         write_u16(a.at(6), m);
+    } else if (a[0] == "resize-image") {   // in.raw nr nc channels scale out.raw: the bilinear resize of read_sample on raw u8 HWC pixels; prints "out_nr out_nc"
+        const long nr = std::stol(a.at(2)), nc = std::stol(a.at(3));
+        const int channels = std::stoi(a.at(4));
+        const double scale = std::stod(a.at(5));
+        const std::string in = annonet_io::slurp(a.at(1));
+        if (channels < 1 || in.size() != (size_t)nr * nc * channels) throw std::runtime_error("raw image file has the wrong size");
+        const long out_nr = (long)std::round(scale * nr), out_nc = (long)std::round(scale * nc);   // as resize_image_bilinear sizes its output
+        if (out_nr < 1 || out_nc < 1) throw std::runtime_error("image is too small for this downscaling factor");
+        std::string out = in;
+        if (scale != 1.0) {   // (scale 1 is the identity, as in resize_image_bilinear)
+            out.assign((size_t)out_nr * out_nc * channels, '\0');
+            resize_bilinear_u8(reinterpret_cast<const uint8_t*>(in.data()), nr, nc, channels, reinterpret_cast<uint8_t*>(&out[0]), out_nr, out_nc);
+        }
+        std::ofstream f(a.at(6), std::ios::binary | std::ios::trunc);
+        f.write(out.data(), (std::streamsize)out.size());
+        std::cout << out_nr << ' ' << out_nc << '\n';
     } else if (a[0] == "confusion" || a[0] == "print-confusion") {   // gt.raw result.raw nr nc classes: the per-pixel and per-region matrices of one image
         const long nr = std::stol(a.at(3)), nc = std::stol(a.at(4));
         const size_t K = std::stoul(a.at(5));

@@ -7,7 +7,10 @@
 // (input directory, gains / detection levels, scan summary, "All N images processed in ... (actual inference: ...)", "Processing time
 // excluding the first image: average = ... ms, max = ... ms", both confusion matrices), the files it reads (annonet.dnn,
 // <image>_mask.png) and writes (<image>_result.png), and its exit codes (2 for option errors, 1 otherwise).
-// Extensions: --precision fp32|bf16, --devices 0,1,... (tile lists sharded over several GPUs from this one process), --dnn <file>.
+// Extensions: --precision fp32|bf16, --devices 0,1,... (tile lists sharded over several GPUs from this one process), --dnn <file>,
+// --host-resize.  A net with a downscaling factor other than 1: the image goes to the GPU at its original size and annonet_infer_scaled()
+// shrinks it, infers and blows the label map back up there (the reference does both resizes on the CPU: annonet.cpp:153 in the readers,
+// annonet_infer_main.cpp:413 in the writers); --host-resize keeps them on this program's reader / writer threads.  Same files, same matrices.
 #define ANNONET_HIP_NO_DLIB
 #include "../../include/annonet_infer_hip.h"
 #include "annonet_host.h"
@@ -23,6 +26,7 @@ struct Settings {
     std::vector<std::string> gain_args, detection_args;
     std::vector<int> devices;
     int max_tile_w = 1024, max_tile_h = 1024;   // the reference's GPU-build defaults (:300-303)
+    bool host_resize = false;
     int readers = (int)std::max(1u, std::thread::hardware_concurrency()), writers = (int)std::max(1u, std::thread::hardware_concurrency());
 };
 
@@ -37,7 +41,8 @@ const char* usage_text() {
            "      --result-image-writer-thread-count arg\n"
            "      --precision fp32|bf16            fp32 = bit-exact parity mode, bf16 = MFMA throughput mode (default)\n"
            "      --devices 0,1,...                GPUs this process drives (tile lists are sharded over them)\n"
-           "      --dnn file                       trained net (default: annonet.dnn)\n";
+           "      --dnn file                       trained net (default: annonet.dnn)\n"
+           "      --host-resize                    downscaled nets: resize image and label map on the CPU threads, not on the GPU\n";
 }
 
 Settings read_command_line(int argc, char** argv) {
@@ -59,7 +64,8 @@ Settings read_command_line(int argc, char** argv) {
         if (option != with_value.end()) {
             if (i + 1 >= argc) throw std::runtime_error("Option '" + word + "' is missing an argument");
             option->second(argv[++i]);
-        } else if (!word.empty() && word[0] == '-') throw std::runtime_error("Option '" + word + "' does not exist");
+        } else if (word == "--host-resize") s.host_resize = true;
+        else if (!word.empty() && word[0] == '-') throw std::runtime_error("Option '" + word + "' does not exist");
         else if (s.directory.empty()) s.directory = word;
         else throw std::runtime_error("Unexpected argument " + word);
     }
@@ -119,13 +125,14 @@ struct TrainedNet {
 // ---- stage 1: readers ----------------------------------------------------------------------------------------------------
 class ImageReaders {
   public:
-    ImageReaders(const std::vector<image_filenames_type>& files, int threads, const std::vector<AnnoClass>& classes, double downscaling)
+    // resize_images = false: the images stay at their original size (annonet_infer_scaled shrinks them on the GPU)
+    ImageReaders(const std::vector<image_filenames_type>& files, int threads, const std::vector<AnnoClass>& classes, double downscaling, bool resize_images)
         : todo_(std::max<size_t>(files.size(), 1)), done_((size_t)std::max(threads, 1)) {
         for (const auto& f : files) todo_.enqueue(f);
         for (int i = 0; i < std::max(threads, 1); ++i)
-            pool_.emplace_back([this, &classes, downscaling] {
+            pool_.emplace_back([this, &classes, downscaling, resize_images] {
                 image_filenames_type names;
-                while (todo_.dequeue(names)) if (!done_.enqueue(read_sample(names, classes, false, downscaling))) break;
+                while (todo_.dequeue(names)) if (!done_.enqueue(read_sample(names, classes, false, downscaling, resize_images))) break;
             });
     }
     ~ImageReaders() { todo_.disable(); done_.disable(); for (auto& t : pool_) if (t.joinable()) t.join(); }
@@ -159,7 +166,7 @@ class ResultWriters {
                 while (jobs_.dequeue(job)) {
                     bool ok = true;
                     try {
-                        resize_label_image(job.labels, job.width, job.height);
+                        if (job.labels.nc() != job.width || job.labels.nr() != job.height) resize_label_image(job.labels, job.width, job.height);   // (a map that annonet_infer_scaled blew up already has the size)
                         painted.set_size(job.labels.nr(), job.labels.nc());
                         auto out = painted.begin();
                         for (const uint16_t label : job.labels) *out++ = label < classes.size() ? classes[label].rgba_label : rgba_ignore_label;   // (65535: an all-NaN pixel)
@@ -221,8 +228,9 @@ int run(const Settings& settings) {
     size_t labelled_pixels = 0;
     InferenceClock clock;
     annonet_infer_temp scratch;
+    const bool resize_on_gpu = trained.downscaling != 1.0 && !settings.host_resize;
     {
-        ImageReaders readers(files, settings.readers, trained.classes, trained.downscaling);
+        ImageReaders readers(files, settings.readers, trained.classes, trained.downscaling, !resize_on_gpu);
         ResultWriters writers(settings.writers, files.size(), trained.classes);
         const auto started = std::chrono::steady_clock::now();
         for (size_t i = 0; i < files.size(); ++i) {
@@ -233,14 +241,17 @@ int run(const Settings& settings) {
             result.width = sample.original_width; result.height = sample.original_height;
 
             const auto t0 = std::chrono::steady_clock::now();
-            annonet_infer(trained.net, sample.input_image, result.labels, scratch, gains, detection_levels, tiles);
+            if (resize_on_gpu) annonet_infer_scaled(trained.net, sample.input_image, trained.downscaling, result.labels, scratch, gains, detection_levels, tiles);
+            else annonet_infer(trained.net, sample.input_image, result.labels, scratch, gains, detection_levels, tiles);
             clock.record(std::chrono::duration_cast<InferenceClock::us>(std::chrono::steady_clock::now() - t0));
+            // both matrices are scored at the net's resolution (the ground truth was resized to it, annonet.cpp:160-166)
+            const dlib::matrix<uint16_t>& scored = resize_on_gpu ? scratch.scaled_result_image : result.labels;
 
             for (const auto& cls_points : sample.labeled_points_by_class) {   // per-pixel score on the annotated pixels (:482-490)
-                for (const dlib::point& p : cls_points.second) per_pixel.add(cls_points.first, result.labels(p.y(), p.x()));
+                for (const dlib::point& p : cls_points.second) per_pixel.add(cls_points.first, scored(p.y(), p.x()));
                 labelled_pixels += cls_points.second.size();
             }
-            region_scorer.score(per_region, sample, result.labels);
+            region_scorer.score(per_region, sample, scored);
             writers.submit(std::move(result));
         }
         clock.report(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - started).count() / 1000.0);

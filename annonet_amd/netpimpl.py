@@ -366,6 +366,77 @@ def annonet_infer_device(net, d_image_ptr, height, width, d_labels_ptr, d_blende
     check(net.L.anh_infer_device(net.h, d_image_ptr, height, width, _ptr(g), C.byref(tp) if tp is not None else None, arr, n, d_labels_ptr, d_blended_ptr))
 
 
+def scaled_dims(height, width, downscaling_factor):
+    """anh_scaled_dims: (scaled height, scaled width) = the size dlib::resize_image(1.0 / factor, img) gives (annonet.cpp:153)."""
+    sh, sw = C.c_int(), C.c_int()
+    check(_lib.lib().anh_scaled_dims(height, width, downscaling_factor, C.byref(sh), C.byref(sw)))
+    return sh.value, sw.value
+
+
+def annonet_infer_scaled(net, input_image, downscaling_factor, gains=None, detection_levels=None, tiling_parameters=None, want_scaled=False, want_blended=False):
+    """read_sample's resize (annonet.cpp:153) + annonet_infer() + resize_label_image (annonet_infer_main.cpp:413) on the device: the image
+    comes at its original size, the label map comes back at that size.  Returns the map, then (when asked for) the map at the net's
+    resolution and the blended class planes at the net's resolution."""
+    img = np.ascontiguousarray(input_image, dtype=np.uint8)
+    if img.ndim == 2:
+        img = img[:, :, None]
+    H, W, c = img.shape
+    if c != net.cfg.in_channels:
+        raise AnnonetHipError(1, "channel count does not match the net input")
+    K = net.cfg.classes
+    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
+    d = np.ascontiguousarray(detection_levels, dtype=np.float64) if detection_levels is not None else None
+    if g is not None and g.size != K or d is not None and d.size != K:
+        raise AnnonetHipError(1, "gains / detection levels need one value per class")
+    sh, sw = scaled_dims(H, W, downscaling_factor)
+    res = np.empty((H, W), np.uint16)
+    scaled = np.empty((sh, sw), np.uint16) if want_scaled else None
+    bl = np.empty((K, sh, sw), np.float32) if want_blended else None
+    tp = tiling_parameters._c() if tiling_parameters is not None else None
+    check(net.L.anh_infer_scaled(net.h, _ptr(img), H, W, downscaling_factor, _ptr(g), _ptr(d), C.byref(tp) if tp is not None else None, _ptr(res), _ptr(scaled), _ptr(bl)))
+    out = (res,) + ((scaled,) if want_scaled else ()) + ((bl,) if want_blended else ())
+    return out if len(out) > 1 else res
+
+
+def annonet_infer_scaled_device(net, d_image_ptr, height, width, downscaling_factor, d_labels_ptr, d_scaled_labels_ptr=0, d_blended_ptr=0, gains=None, tiling_parameters=None):
+    """annonet_infer_scaled with the original-size image, the original-size label map and (optionally) the map and the planes at the
+    net's resolution resident in HBM (device pointers as ints); enqueued on the handle's stream, not synchronised."""
+    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
+    tp = tiling_parameters._c() if tiling_parameters is not None else None
+    check(net.L.anh_infer_scaled_device(net.h, d_image_ptr, height, width, downscaling_factor, _ptr(g), C.byref(tp) if tp is not None else None,
+                                        d_labels_ptr, d_scaled_labels_ptr or None, d_blended_ptr or None))
+
+
+def _through_device(src, out_shape, dtype, prefill, launch):
+    """host array -> HBM -> `launch(src_ptr, dst_ptr, stream)` -> host array (torch moves the bytes)"""
+    import torch
+    d_src = torch.from_numpy(src.view(np.uint8).reshape(-1)).cuda()
+    n = int(np.prod(out_shape)) * np.dtype(dtype).itemsize
+    d_dst = torch.empty(n, dtype=torch.uint8, device="cuda") if prefill is None else torch.full((n,), int(prefill) & 255, dtype=torch.uint8, device="cuda")
+    launch(d_src.data_ptr(), d_dst.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.current_stream().synchronize()
+    return d_dst.cpu().numpy().view(dtype).reshape(out_shape)
+
+
+def resize_image(img, out_h, out_w, prefill=None):
+    """The device's bilinear resize (anh_resize_image_device) on a host u8 image [H,W] / [H,W,1] / [H,W,3]; `prefill`: byte the
+    destination is filled with before the kernel runs (tests: every output element must be written)."""
+    a = np.ascontiguousarray(img, dtype=np.uint8)
+    c = 1 if a.ndim == 2 else a.shape[2]
+    L = _lib.lib()
+    return _through_device(a, (out_h, out_w) + a.shape[2:], np.uint8, prefill,
+                           lambda s, d, st: check(L.anh_resize_image_device(s, c, a.shape[0], a.shape[1], d, out_h, out_w, st)))
+
+
+def resize_labels(lab, out_w, out_h, prefill=None):
+    """The device's nearest-neighbour resize (anh_resize_labels_device) on a host u16 label map; arguments as resize_label_image
+    (annonet.cpp:134: target width, then target height)."""
+    a = np.ascontiguousarray(lab, dtype=np.uint16)
+    L = _lib.lib()
+    return _through_device(a, (out_h, out_w), np.uint16, prefill,
+                           lambda s, d, st: check(L.anh_resize_labels_device(s, a.shape[0], a.shape[1], d, out_h, out_w, st)))
+
+
 def argmax_device(net, d_blended_ptr, height, width, row0, row1, d_labels_ptr, gains=None):
     """find_label (annonet_infer.cpp:170-185) over rows [row0, row1) of device-resident blended planes."""
     g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None

@@ -156,6 +156,31 @@ int anh_infer(anh_runtime* h, const uint8_t* image_hwc, int height, int width,
 int anh_infer_device(anh_runtime* h, const uint8_t* d_image_hwc, int height, int width,
                      const double* gains, const anh_tiling_params* tiling,
                      const anh_tile* tiles, size_t n_tiles, uint16_t* d_result_labels, float* d_blended);
+/* ---- downscaled inference: a net trained with a downscaling factor (annonet.dnn carries it) sees every image shrunk by it ----
+ * read_sample shrinks the image with dlib::resize_image(1.0 / factor, image), bilinear (annonet.cpp:153); the inference program blows the
+ * label map back up with resize_label_image, nearest neighbour (annonet_infer_main.cpp:413, annonet.cpp:132-141).  Both run on the device
+ * here, with the arithmetic of annonet_amd/host/annonet_host.h (dlib's sampling grid is restated there [UPSTREAM-UNVERIFIED]): bit-exact
+ * against that host code, any source and destination size.
+ * anh_scaled_dims: the size dlib::resize_image(1.0 / factor, img) gives: round(height * (1.0 / factor)), round(width * (1.0 / factor))
+ * — the factor is inverted first, as read_sample does.  Any factor > 0 whose scaled sides stay within 1..32768 is accepted. */
+int anh_scaled_dims(int height, int width, double downscaling_factor, int* scaled_height, int* scaled_width);
+/* the two resizes on their own, device-resident, enqueued on the given stream: u8 HWC image with 1 or 3 channels; u16 label map */
+int anh_resize_image_device(const uint8_t* d_src_hwc, int channels, int src_h, int src_w, uint8_t* d_dst_hwc, int dst_h, int dst_w, void* hip_stream);
+int anh_resize_labels_device(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w, void* hip_stream);
+/* read_sample's resize + annonet_infer() + resize_label_image in one call: image_hwc comes at its ORIGINAL size height x width.
+ * result_labels: height x width (original size).  scaled_labels (optional): the map at the net's resolution (anh_scaled_dims), as
+ * annonet_infer() leaves it — the inference program scores on it (annonet_infer_main.cpp:482-492).  blended_out (optional): K planes at
+ * the net's resolution.  The detection-level filter runs at the net's resolution, before the map is blown up, as in the reference.
+ * downscaling_factor == 1 returns exactly what anh_infer returns.  On a handle with several replicas every replica shrinks the image
+ * itself and replica 0 blows up the merged map. */
+int anh_infer_scaled(anh_runtime* h, const uint8_t* image_hwc, int height, int width, double downscaling_factor,
+                     const double* gains, const double* detection_levels, const anh_tiling_params* tiling,
+                     uint16_t* result_labels, uint16_t* scaled_labels, float* blended_out);
+/* the same with the image and the maps resident in HBM, enqueued on the handle's stream without synchronising: d_result_labels
+ * height x width; d_scaled_labels (optional) and d_blended (optional, K planes) at the net's resolution */
+int anh_infer_scaled_device(anh_runtime* h, const uint8_t* d_image_hwc, int height, int width, double downscaling_factor,
+                            const double* gains, const anh_tiling_params* tiling,
+                            uint16_t* d_result_labels, uint16_t* d_scaled_labels, float* d_blended);
 /* label rows [row0, row1) of device-resident blended planes (find_label, annonet_infer.cpp:170-185): the second half of a
    sharded annonet_infer(), run after the ranks have exchanged the plane sums of their overlapping tiles */
 int anh_argmax_device(anh_runtime* h, const float* d_blended, int height, int width, int row0, int row1, const double* gains, uint16_t* d_result);

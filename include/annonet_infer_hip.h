@@ -28,6 +28,7 @@ struct annonet_infer_temp {  // annonet_infer.h:26-32; the GPU path keeps its sc
     dlib::matrix<unsigned int> connected_blobs;
     std::vector<dlib::matrix<float>> blended_output;  // filled when keep_blended_output is set (see above for its default)
     bool keep_blended_output = annonet_hip_keep_blended_default();
+    dlib::matrix<uint16_t> scaled_result_image;       // annonet_infer_scaled: the label map at the net's resolution, filled on every scaled call
 };
 
 inline void annonet_infer(NetPimpl::RuntimeNet& net, const NetPimpl::input_type& input_image, dlib::matrix<uint16_t>& result_image,
@@ -51,6 +52,40 @@ inline void annonet_infer(NetPimpl::RuntimeNet& net, const NetPimpl::input_type&
         for (int k = 0; k < K; ++k) {
             temp.blended_output[k].set_size(H, W);
             std::copy(planes.begin() + (size_t)k * H * W, planes.begin() + (size_t)(k + 1) * H * W, temp.blended_output[k].begin());
+        }
+    }
+}
+
+// What the reference's inference program does around annonet_infer() for a net trained with a downscaling factor, in one call on the
+// GPU: read_sample's dlib::resize_image(1.0 / factor, image) (annonet.cpp:153, bilinear), annonet_infer() on the shrunk image
+// (annonet_infer_main.cpp:468) and resize_label_image back to the original size (annonet_infer_main.cpp:413, annonet.cpp:132-141, nearest
+// neighbour).  input_image comes at its ORIGINAL size; result_image has that size; temp.scaled_result_image is the map at the net's
+// resolution, which the program scores its confusion matrices on (annonet_infer_main.cpp:482-492).  temp.blended_output keeps its
+// keep_blended_output rule and holds the planes at the net's resolution.
+inline void annonet_infer_scaled(NetPimpl::RuntimeNet& net, const NetPimpl::input_type& input_image, double downscaling_factor,
+                                 dlib::matrix<uint16_t>& result_image, annonet_infer_temp& temp, const std::vector<double>& gains = std::vector<double>(),
+                                 const std::vector<double>& detection_levels = std::vector<double>(),
+                                 const tiling::parameters& tiling_parameters = tiling::parameters()) {
+    anh_net_config cfg;
+    NetPimpl::check(anh_runtime_config(net.handle(), &cfg));
+    const int K = cfg.classes, H = (int)input_image.nr(), W = (int)input_image.nc();
+    if (!gains.empty() && (int)gains.size() != K) throw std::runtime_error("annonet_infer_scaled: one gain per class expected");
+    if (!detection_levels.empty() && (int)detection_levels.size() != K) throw std::runtime_error("annonet_infer_scaled: one detection level per class expected");
+    int sh = 0, sw = 0;
+    NetPimpl::check(anh_scaled_dims(H, W, downscaling_factor, &sh, &sw));
+    result_image.set_size(H, W);
+    temp.scaled_result_image.set_size(sh, sw);
+    std::vector<float> planes;
+    if (temp.keep_blended_output) planes.resize((size_t)K * sh * sw);
+    anh_tiling_params tp{tiling_parameters.max_tile_width, tiling_parameters.max_tile_height, tiling_parameters.overlap_x, tiling_parameters.overlap_y};
+    NetPimpl::check(anh_infer_scaled(net.handle(), reinterpret_cast<const uint8_t*>(&*input_image.begin()), H, W, downscaling_factor,
+                                     gains.empty() ? nullptr : gains.data(), detection_levels.empty() ? nullptr : detection_levels.data(), &tp,
+                                     &*result_image.begin(), &*temp.scaled_result_image.begin(), temp.keep_blended_output ? planes.data() : nullptr));
+    if (temp.keep_blended_output) {
+        temp.blended_output.resize(K);
+        for (int k = 0; k < K; ++k) {
+            temp.blended_output[k].set_size(sh, sw);
+            std::copy(planes.begin() + (size_t)k * sh * sw, planes.begin() + (size_t)(k + 1) * sh * sw, temp.blended_output[k].begin());
         }
     }
 }
