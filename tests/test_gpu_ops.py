@@ -32,6 +32,11 @@ SHAPES = [
     ((0, 1, 1, 0, 32, 3), 2, 17, 13),     # head
     ((0, 3, 1, 1, 8, 16), 1, 12, 10),     # narrow nets (width scaler < 1)
     ((0, 3, 1, 1, 40, 24), 1, 10, 13),    # widths that are not multiples of 32
+    ((0, 1, 1, 0, 32, 5), 2, 17, 13),     # heads of more than four classes: past every fused tail, a plain conv with cout = K
+    ((0, 1, 1, 0, 32, 9), 2, 17, 13),     # ... odd reduction length in backward-data (two channels per fp32 MFMA)
+    ((0, 1, 1, 0, 32, 33), 1, 11, 14),    # ... one output channel past a tile of 32
+    ((0, 1, 1, 0, 32, 64), 1, 11, 14),    # ... the largest class count spec.cpp accepts
+    ((0, 1, 1, 0, 8, 9), 1, 12, 10),      # ... the head of a narrow net
 ]
 
 
