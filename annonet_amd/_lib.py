@@ -75,6 +75,30 @@ class OpBnDy(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("da", "y", "scale", "shift", "mean", "invstd", "coef")]
 
 
+class OpBnLayer(C.Structure):   # anh_op_bn_layer
+    _fields_ = [("c", C.c_int), ("pixels", C.c_double), ("eps", C.c_float), ("af", C.c_double), ("unbias", C.c_double)] + \
+               [(n, C.c_void_p) for n in ("sums", "gamma", "beta", "running_mean", "running_var", "mean", "invstd", "scale", "shift", "var")]
+
+
+class OpBnInput(C.Structure):   # anh_op_bn_input
+    _fields_ = [(n, C.c_void_p) for n in ("x", "scale", "shift", "sums", "gamma", "beta")] + [("eps", C.c_float)]
+
+
+class OpBnBwd(C.Structure):   # anh_op_bn_bwd
+    _fields_ = [("c", C.c_int), ("head_k", C.c_int), ("pixels", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("da", "y", "gamma", "mean", "invstd", "scale", "shift", "head_g", "head_w_tm", "coef_in")] + \
+               [("tables", C.c_int), ("out_of_place", C.c_int), ("stages", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("sums", "dgamma", "dbeta", "coef", "dy")] + [("ticket", C.c_int64), ("workgroups", C.c_int)]
+
+
+class OpHead(C.Structure):   # anh_op_head
+    _fields_ = [("k", C.c_int), ("pixels", C.c_int64), ("scale", C.c_double), ("a", C.POINTER(OpBnInput)), ("b", C.POINTER(OpBnInput))] + \
+               [(n, C.c_void_p) for n in ("w_tm", "bias", "labels", "weights")] + [("da_virtual", C.c_int), ("bn_sums", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("bn_mean", "bn_invstd", "bn_gamma")] + [("fold_jobs", C.POINTER(OpBnLayer)), ("n_fold_jobs", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("logits", "dlogits", "da", "loss", "dbias", "dw", "bn_sums_out", "dgamma", "dbeta", "coef")] + \
+               [("error_flag", C.c_int), ("ticket", C.c_int64), ("workgroups", C.c_int)]
+
+
 class TilingParams(C.Structure):
     _fields_ = [("max_tile_width", C.c_int), ("max_tile_height", C.c_int), ("overlap_x", C.c_int), ("overlap_y", C.c_int)]
 
@@ -184,6 +208,14 @@ _SIGNATURES = {  # ConvDesc / OpInput are defined above
     "anh_op_conv_forward_stats": (C.c_int, [C.c_int, C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_int, C.POINTER(OpInput), C.POINTER(OpInput), _P, _P, _P, C.POINTER(C.c_int)]),
     "anh_op_conv_backward_data_bn": (C.c_int, [C.c_int, C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int)]),
     "anh_op_conv_backward_filter_bn": (C.c_int, [C.c_int, C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_int, _P, C.POINTER(OpBnDy), _P, C.POINTER(C.c_int)]),
+    "anh_op_bn_fold": (C.c_int, [C.POINTER(OpBnLayer), C.c_int, C.c_uint64]),
+    "anh_op_bn_forward_stats": (C.c_int, [C.c_int, _P, C.POINTER(OpBnLayer), _P]),
+    "anh_op_conv_forward_stats_table": (C.c_int, [C.c_int, C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_int, _P, C.POINTER(OpBnInput), C.POINTER(OpBnInput), _P, C.c_int,
+                                                  _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "anh_op_conv_backward_data_bn_table": (C.c_int, [C.c_int, C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_int] + [_P] * 14 + [C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "anh_op_bn_backward": (C.c_int, [C.c_int, C.POINTER(OpBnBwd)]),
+    "anh_op_head_train": (C.c_int, [C.c_int, C.POINTER(OpHead)]),
+    "anh_op_loss": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_double, _P, _P, _P, C.POINTER(C.c_int)]),
     "anh_get_tiles": (C.c_int, [C.c_int, C.c_int, C.POINTER(TilingParams), C.POINTER(C.POINTER(Tile)), C.POINTER(C.c_size_t)]),
     "anh_set_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_double, _P]),
     "anh_random_rect_containing_point": (C.c_int, [C.c_uint32, C.c_uint32, C.c_long, C.c_long, C.c_long, C.c_long, C.POINTER(Rect)]),

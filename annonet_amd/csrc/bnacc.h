@@ -27,6 +27,47 @@ enum { BNACC_SUM_Y = 0, BNACC_SUM_YY = 1, BNACC_SUM_DZ_XHAT = 2, BNACC_SUM_DZ = 
 constexpr int kBnAccReplicas = 16;
 __host__ __device__ inline size_t bnacc_words(int c) { return (size_t)kBnAccReplicas * 8 * c + 8; }
 
+// Host side of a table (the single-op entry points of ops.cpp): a table written word by word without bnacc_add, and read back.
+// bnacc_split_host: v as (hi, lo) words; false when v is out of range or not exactly hi * 2^-8 + lo * 2^-60.
+__host__ inline bool bnacc_split_host(double v, long long& hi, long long& lo) {
+    if (!(std::fabs(v) < 3.0e16)) return false;
+    const double h = std::rint(v * 256.0);
+    const double r = (v - h * (1.0 / 256.0)) * 1152921504606846976.0;   // exact: the subtraction and the scaling by 2^60
+    hi = (long long)h; lo = (long long)std::rint(r);
+    return (double)lo == r;
+}
+// bnacc_spread_host: ADDS (hi, lo) to the table as kBnAccReplicas unequal shares of mixed sign (integers: the shares add up exactly);
+// `state` is a splitmix64 stream that picks the shares.
+__host__ inline void bnacc_spread_host(long long* table, int which, int c, int ch, long long hi, long long lo, unsigned long long& state) {
+    auto draw = [&state]() {
+        unsigned long long z = (state += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    };
+    long long left_hi = hi, left_lo = lo;
+    for (int r = 0; r < kBnAccReplicas; ++r) {
+        long long* p = table + (size_t)r * 8 * c + ((size_t)which * c + ch) * 2;
+        long long share_hi = left_hi, share_lo = left_lo;
+        if (r + 1 < kBnAccReplicas) {   // a share of up to 42 / 50 bits of either sign, at least 1 in magnitude; the last copy takes what is left
+            share_hi = (long long)(draw() >> (22 + r % 7)) * ((r & 1) ? -1 : 1) + ((r & 1) ? -1 : 1);
+            share_lo = (long long)(draw() >> (14 + r % 5)) * ((r & 2) ? -1 : 1) + ((r & 2) ? -1 : 1);
+        }
+        p[0] += share_hi; p[1] += share_lo;
+        left_hi -= share_hi; left_lo -= share_lo;
+    }
+}
+// the total of one sum, with bnacc_get's arithmetic (poison ignored: read the word at bnacc_poison_index)
+__host__ inline double bnacc_total_host(const long long* table, int which, int c, int ch) {
+    long long hi = 0, lo = 0;
+    for (int r = 0; r < kBnAccReplicas; ++r) {
+        const long long* p = table + (size_t)r * 8 * c + ((size_t)which * c + ch) * 2;
+        hi += p[0]; lo += p[1];
+    }
+    return (double)hi * (1.0 / 256.0) + (double)lo * (1.0 / 1152921504606846976.0);
+}
+__host__ __device__ inline size_t bnacc_poison_index(int c) { return (size_t)kBnAccReplicas * 8 * c; }       // then the ticket counter
+
 #if defined(__HIPCC__)
 __device__ __forceinline__ void bnacc_add(long long* acc, int which, int c, int ch, double v) {
     const double k_hi = 256.0, k_lo = 1152921504606846976.0;   // 2^8, 2^60

@@ -325,6 +325,7 @@ void launch_conv_mfma(const ConvArgs& a, hipStream_t s);
 // value is the number of partials per channel to pass to launch_bn_forward_finalize)
 int conv_fused_stat_blocks(const ConvArgs& a);
 int conv_fused_bnred_blocks(const ConvArgs& a);   // same for ConvArgs::bnred_partials (backward-data convs)
+int conv_mfma_workgroups(const ConvArgs& a);      // workgroups of the persistent kernel's launch (what a table's ticket counts up to); 0: another kernel
 bool conv_folds_bn_tables(const ConvArgs& a);     // the layer's kernel reads Src::a_tab / b_tab (the persistent kernels)
 bool conv_stores_activation(const ConvArgs& a);   // the layer's MFMA kernel honours ConvArgs::out_scale / out_shift (src.kind SRC_RAW, SRC_SUM2 or SRC_IMAGE)
 bool mfma_wgrad_supported(const WgradArgs& a);

@@ -2703,6 +2703,13 @@ int conv_fused_bnred_blocks(const ConvArgs& a) {
     return p.grid_x;
 }
 
+int conv_mfma_workgroups(const ConvArgs& a) {
+    if (!mfma_conv_supported(a)) return 0;
+    if (stem_mfma_ok(a)) return stem_mfma_blocks(a);
+    const ConvPlan p = conv_plan(a);
+    return p.form == 2 ? p.grid_x * p.groups : 0;
+}
+
 void launch_conv_mfma(const ConvArgs& a, hipStream_t s) {
     if (!mfma_conv_supported(a)) fail(ANH_ERR_INTERNAL, "conv_mfma: unsupported shape");
     if ((int64_t)a.n * a.h_out * a.w_out == 0) return;

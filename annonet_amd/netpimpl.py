@@ -747,3 +747,179 @@ def op_conv_backward_filter(precision, desc, xa, sa=None, ta=None, xb=None, sb=N
     check(_lib.lib().anh_op_conv_backward_filter(precision, C.byref(d), n, h, w, C.byref(a), C.byref(b) if b is not None else None,
                                                  _ptr(g), _ptr(dw), C.byref(used)))
     return dw, bool(used.value)
+
+
+# ---- table mode and the training kernels that are not convolutions (include/annonet_hip.h, tests/test_gpu_train_ops.py) ----
+def _f32(a, keep):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    keep.append(a)
+    return a.ctypes.data
+
+
+def _bn_layer(spec, keep):
+    """spec: dict(c, pixels, gamma, beta, eps[, sums, running_mean, running_var, af, unbias]) -> (OpBnLayer, outputs dict)"""
+    c = int(spec["c"])
+    out = {n: np.full(c, np.nan, np.float32) for n in ("mean", "invstd", "scale", "shift")}
+    out["var"] = np.full(c, np.nan, np.float64)
+    L = _lib.OpBnLayer()
+    L.c, L.pixels, L.eps, L.af, L.unbias = c, float(spec["pixels"]), float(spec.get("eps", 1e-4)), float(spec.get("af", 1.0)), float(spec.get("unbias", 1.0))
+    if spec.get("sums") is not None:
+        sums = np.ascontiguousarray(spec["sums"], dtype=np.float64)
+        assert sums.shape == (c, 2)
+        keep.append(sums)
+        L.sums = sums.ctypes.data
+    L.gamma, L.beta = _f32(spec["gamma"], keep), _f32(spec["beta"], keep)
+    if spec.get("running_mean") is not None:
+        out["running_mean"] = np.array(spec["running_mean"], dtype=np.float32)
+        out["running_var"] = np.array(spec["running_var"], dtype=np.float32)
+        L.running_mean, L.running_var = out["running_mean"].ctypes.data, out["running_var"].ctypes.data
+    for n in ("mean", "invstd", "scale", "shift", "var"):
+        setattr(L, n, out[n].ctypes.data)
+    return L, out
+
+
+def op_bn_fold(jobs, spread_seed=1):
+    """ONE bn_fold_all launch over up to 16 jobs (dicts as _bn_layer takes, with sums [c, 2] = (sum y, sum y^2)).
+    Returns one dict per job: mean, invstd, scale, shift, var[, running_mean, running_var]."""
+    keep, outs = [], []
+    arr = (_lib.OpBnLayer * len(jobs))()
+    for i, j in enumerate(jobs):
+        arr[i], o = _bn_layer(j, keep)
+        outs.append(o)
+    check(_lib.lib().anh_op_bn_fold(arr, len(jobs), spread_seed))
+    return outs
+
+
+def op_bn_forward_stats(precision, y, gamma, beta, eps=1e-4, running_mean=None, running_var=None, af=1.0, unbias=1.0):
+    """The partials form: statistics kernel over y [P, C] + finalize.  Returns (arrays dict as op_bn_fold, sums [C, 2])."""
+    keep = []
+    yy = np.ascontiguousarray(y, dtype=np.float32)
+    p, c = yy.shape
+    L, out = _bn_layer(dict(c=c, pixels=p, gamma=gamma, beta=beta, eps=eps, running_mean=running_mean, running_var=running_var, af=af, unbias=unbias), keep)
+    sums = np.empty((c, 2), np.float64)
+    check(_lib.lib().anh_op_bn_forward_stats(precision, _ptr(yy), C.byref(L), _ptr(sums)))
+    return out, sums
+
+
+def _bn_input(spec, keep):
+    """spec: dict(x, scale, shift) or dict(x, sums, gamma, beta[, eps]) (table form)"""
+    if spec is None:
+        return None
+    i = _lib.OpBnInput()
+    i.x = _f32(spec["x"], keep)
+    if spec.get("sums") is not None:
+        sums = np.ascontiguousarray(spec["sums"], dtype=np.float64)
+        keep.append(sums)
+        i.sums, i.gamma, i.beta, i.eps = sums.ctypes.data, _f32(spec["gamma"], keep), _f32(spec["beta"], keep), float(spec.get("eps", 1e-4))
+    else:
+        i.scale, i.shift = _f32(spec["scale"], keep), _f32(spec["shift"], keep)
+    return i
+
+
+def op_conv_forward_stats_table(precision, desc, a=None, b=None, image=None, filters=None, tables=True):
+    """Forward conv with its bn statistics added into a table (tables) or left as partials; a / b as _bn_input takes, or a u8 image (the stem).
+    Returns dict(y, sums [cout, 2], poison, ticket, workgroups)."""
+    keep = []
+    ia, ib = _bn_input(a, keep), _bn_input(b, keep)
+    img = None if image is None else np.ascontiguousarray(image, dtype=np.uint8)
+    n, h, w, _ = img.shape if img is not None else np.shape(a["x"])
+    d = _lib.ConvDesc(*desc)
+    f = np.ascontiguousarray(filters, dtype=np.float32)
+    y = np.empty((n, _out_dim(desc, h), _out_dim(desc, w), desc[5]), np.float32)
+    sums = np.empty((desc[5], 2), np.float64)
+    poison, ticket, wgs = C.c_int64(-1), C.c_int64(-1), C.c_int(0)
+    check(_lib.lib().anh_op_conv_forward_stats_table(precision, C.byref(d), n, h, w, _ptr(img), C.byref(ia) if ia is not None else None,
+                                                     C.byref(ib) if ib is not None else None, _ptr(f), int(bool(tables)), _ptr(y), _ptr(sums),
+                                                     C.byref(poison), C.byref(ticket), C.byref(wgs)))
+    return dict(y=y, sums=sums, poison=poison.value, ticket=ticket.value, workgroups=wgs.value)
+
+
+def op_conv_backward_data_bn_table(precision, desc, dy, filters, in_hw, y_prev, scale, shift, mean, invstd, gamma, dx_init=None):
+    """op_conv_backward_data_bn with the sums in a table and the finish by the launch's last workgroup.
+    Returns dict(dx, sums [cin, 2], dgamma, dbeta, coef [3, cin], ticket, workgroups)."""
+    d = _lib.ConvDesc(*desc)
+    g = np.ascontiguousarray(dy, dtype=np.float32)
+    f = np.ascontiguousarray(filters, dtype=np.float32)
+    n, cin = g.shape[0], desc[4]
+    arrs = [np.ascontiguousarray(v, dtype=np.float32) for v in (y_prev, scale, shift, mean, invstd, gamma)]
+    init = None if dx_init is None else np.ascontiguousarray(dx_init, dtype=np.float32)
+    dx = np.empty((n, in_hw[0], in_hw[1], cin), np.float32)
+    sums = np.empty((cin, 2), np.float64)
+    dgamma, dbeta, coef = np.empty(cin, np.float32), np.empty(cin, np.float32), np.empty((3, cin), np.float32)
+    ticket, wgs = C.c_int64(-1), C.c_int(0)
+    check(_lib.lib().anh_op_conv_backward_data_bn_table(precision, C.byref(d), n, in_hw[0], in_hw[1], _ptr(g), _ptr(f), _ptr(init), *[_ptr(v) for v in arrs],
+                                                        _ptr(dx), _ptr(sums), _ptr(dgamma), _ptr(dbeta), _ptr(coef), C.byref(ticket), C.byref(wgs)))
+    return dict(dx=dx, sums=sums, dgamma=dgamma, dbeta=dbeta, coef=coef, ticket=ticket.value, workgroups=wgs.value)
+
+
+def op_bn_backward(precision, y, mean, invstd, scale, shift, da=None, gamma=None, tables=False, out_of_place=False, stages=7, coef_in=None,
+                   head_g=None, head_w_tm=None):
+    """bn + relu backward on (da, y) [P, C]: stages & 1 reduce, & 2 finalize, & 4 apply (see anh_op_bn_bwd).
+    Returns dict(sums [C, 2], dgamma, dbeta, coef [3, C], dy [P, C], ticket, workgroups)."""
+    keep = []
+    yy = np.ascontiguousarray(y, dtype=np.float32)
+    p, c = yy.shape
+    o = _lib.OpBnBwd()
+    o.c, o.pixels, o.y = c, p, yy.ctypes.data
+    o.da, o.gamma, o.mean, o.invstd, o.scale, o.shift = (_f32(v, keep) for v in (da, gamma, mean, invstd, scale, shift))
+    o.coef_in, o.head_g, o.head_w_tm = (_f32(v, keep) for v in (coef_in, head_g, head_w_tm))
+    o.head_k = 0 if head_g is None else np.shape(head_g)[1]
+    o.tables, o.out_of_place, o.stages = int(bool(tables)), int(bool(out_of_place)), stages
+    out = dict(sums=np.full((c, 2), np.nan, np.float64), dgamma=np.empty(c, np.float32), dbeta=np.empty(c, np.float32), coef=np.empty((3, c), np.float32),
+               dy=np.full((p, c), np.nan, np.float32))
+    for n in ("sums", "dgamma", "dbeta", "coef", "dy"):
+        setattr(o, n, out[n].ctypes.data)
+    check(_lib.lib().anh_op_bn_backward(precision, C.byref(o)))
+    out.update(ticket=o.ticket, workgroups=o.workgroups)
+    return out
+
+
+def op_head_train(precision, a, b, w_tm, bias, labels, weights, scale, da_virtual=False, bn_sums=0, bn_mean=None, bn_invstd=None, bn_gamma=None,
+                  fold_jobs=()):
+    """The fused tail of a training step (anh_op_head).  a / b as _bn_input takes, x = [P, 32]; w_tm [32, K]; bn_sums 0 / 1 (partials) / 2 (table + finish).
+    Returns dict(logits, dlogits [P, K], da [P, 32] or None, loss, dbias, dw [32, K], bn_sums [32, 2], dgamma, dbeta, coef [3, 32], error_flag, ticket,
+    workgroups, folds = one dict per fold job)."""
+    keep = []
+    ia, ib = _bn_input(a, keep), _bn_input(b, keep)
+    p = np.shape(a["x"])[0]
+    w = np.ascontiguousarray(w_tm, dtype=np.float32)
+    k = w.shape[1]
+    lab = np.ascontiguousarray(labels, dtype=np.uint16)
+    o = _lib.OpHead()
+    o.k, o.pixels, o.scale = k, p, float(scale)
+    o.a = C.pointer(ia)
+    if ib is not None:
+        o.b = C.pointer(ib)
+    o.w_tm, o.bias, o.labels, o.weights = w.ctypes.data, _f32(bias, keep), lab.ctypes.data, _f32(weights, keep)
+    o.da_virtual, o.bn_sums = int(bool(da_virtual)), bn_sums
+    o.bn_mean, o.bn_invstd, o.bn_gamma = (_f32(v, keep) for v in (bn_mean, bn_invstd, bn_gamma))
+    jobs = (_lib.OpBnLayer * max(len(fold_jobs), 1))()
+    folds = []
+    for i, j in enumerate(fold_jobs):
+        jobs[i], fo = _bn_layer(j, keep)
+        folds.append(fo)
+    o.fold_jobs, o.n_fold_jobs = jobs, len(fold_jobs)
+    out = dict(logits=np.empty((p, k), np.float32), dlogits=np.empty((p, k), np.float32), da=None if da_virtual else np.empty((p, 32), np.float32),
+               loss=np.empty(1, np.float64), dbias=np.empty(k, np.float32), dw=np.empty((32, k), np.float32), bn_sums=np.full((32, 2), np.nan, np.float64),
+               dgamma=np.empty(32, np.float32), dbeta=np.empty(32, np.float32), coef=np.empty((3, 32), np.float32))
+    for n in ("logits", "dlogits", "loss", "dbias", "dw", "dgamma", "dbeta", "coef"):
+        setattr(o, n, out[n].ctypes.data)
+    o.bn_sums_out = out["bn_sums"].ctypes.data
+    if not da_virtual:
+        o.da = out["da"].ctypes.data
+    check(_lib.lib().anh_op_head_train(precision, C.byref(o)))
+    out.update(loss=float(out["loss"][0]), error_flag=o.error_flag, ticket=o.ticket, workgroups=o.workgroups, folds=folds)
+    return out
+
+
+def op_loss(logits, labels, weights, scale):
+    """The unfused loss kernel on fp32 logits [P, K].  Returns dict(dlogits, loss, dbias, error_flag)."""
+    z = np.ascontiguousarray(logits, dtype=np.float32)
+    p, k = z.shape
+    lab = np.ascontiguousarray(labels, dtype=np.uint16)
+    wgt = np.ascontiguousarray(weights, dtype=np.float32)
+    g, loss, dbias, err = np.empty((p, k), np.float32), np.empty(1, np.float64), np.empty(k, np.float32), C.c_int(0)
+    check(_lib.lib().anh_op_loss(_ptr(z), _ptr(lab), _ptr(wgt), p, k, float(scale), _ptr(g), _ptr(loss), _ptr(dbias), C.byref(err)))
+    return dict(dlogits=g, loss=float(loss[0]), dbias=dbias, error_flag=err.value)

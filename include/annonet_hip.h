@@ -297,6 +297,78 @@ int anh_op_conv_backward_data_bn(int precision, const anh_conv_desc* d, int n, i
 int anh_op_conv_backward_filter_bn(int precision, const anh_conv_desc* d, int n, int h_in, int w_in, const uint8_t* image_u8,
                                    const anh_op_bn_dy* dy, float* dw_canonical, int* computed_dy_in_kernel);
 
+/* ---- the batch-norm accumulator-table forms ("table mode", the default of the bf16 training step) and the training kernels that are
+ * not convolutions, one at a time on host tensors (tests/test_gpu_train_ops.py).  A table is built on the host from per-channel sums
+ * (each split into its two words and spread unevenly over every replica of the table) and decoded on the host the same way.
+ *
+ * anh_op_bn_layer   one bn layer of c channels over `pixels` values per channel.  In: sums[2*c] = per channel (sum y, sum y*y) where a
+ *                   table is built from them (each must be a multiple of 2^-60 below 3e16), gamma, beta, eps, and the running statistics
+ *                   (in / out; NULL = no running update) with their averaging factor and unbias factor.  Out: mean, invstd, scale, shift [c]
+ *                   and the biased variance var[c]. */
+typedef struct {
+    int c; double pixels; float eps; double af, unbias;
+    const double* sums; const float* gamma; const float* beta;
+    float* running_mean; float* running_var;
+    float* mean; float* invstd; float* scale; float* shift; double* var;
+} anh_op_bn_layer;
+/* ONE launch of the fold kernel over n_jobs <= 16 layers, each from its own table */
+int anh_op_bn_fold(anh_op_bn_layer* jobs, int n_jobs, uint64_t spread_seed);
+/* the partials form of the same arrays: statistics kernel over y[pixels][c] + finalize; sums_out[2*c] = the totals of its partials */
+int anh_op_bn_forward_stats(int precision, const float* y, anh_op_bn_layer* layer, double* sums_out);
+
+/* An input of a table-mode consumer: the producer's raw output x plus EITHER its folded (scale, shift) OR (sums != NULL) its sums,
+ * gamma, beta and eps — a table is built from them and the kernel folds (scale, shift) in its prologue (pixels = those of x). */
+typedef struct { const float* x; const float* scale; const float* shift; const double* sums; const float* gamma; const float* beta; float eps; } anh_op_bn_input;
+/* anh_op_conv_forward_stats with the forms the engine's table mode uses.  image_u8 != NULL: the stem, reading a u8 NHWC image (a, b NULL).
+ * tables = 0: per-workgroup partials (as anh_op_conv_forward_stats; requires the conv kernel to fuse them); tables = 1: the kernel adds into
+ * a zeroed table; sums[2*cout] = the decoded totals, *poison / *ticket = the table's two control words, *workgroups = the launch's. */
+int anh_op_conv_forward_stats_table(int precision, const anh_conv_desc* d, int n, int h_in, int w_in, const uint8_t* image_u8,
+                                    const anh_op_bn_input* a, const anh_op_bn_input* b, const float* filters_canonical, int tables,
+                                    float* y_nhwc, double* sums, int64_t* poison, int64_t* ticket, int* workgroups);
+/* anh_op_conv_backward_data_bn with the sums added to a zeroed table and folded by the launch's last workgroup: dgamma[cin], dbeta[cin],
+ * coef[3*cin] = [gamma*invstd | sum dz / P | sum dz*xhat / P] (prefilled with NaN), *ticket = the table's counter afterwards. */
+int anh_op_conv_backward_data_bn_table(int precision, const anh_conv_desc* d, int n, int h_in, int w_in, const float* dy_nhwc,
+                                       const float* filters_canonical, const float* dx_init, const float* y_prev, const float* scale,
+                                       const float* shift, const float* mean, const float* invstd, const float* gamma, float* dx_nhwc,
+                                       double* sums, float* dgamma, float* dbeta, float* coef, int64_t* ticket, int* workgroups);
+
+/* bn + relu backward of one layer on (da, y)[pixels][c]: stages & 1 = reduce, & 2 = finalize, & 4 = apply.  tables = 1: the reduce adds
+ * into a zeroed table and its last workgroup is the finish (no finalize kernel; vector widths only).  Without stage 2 the apply reads
+ * coef_in[3*c].  Head form (head_g[pixels][head_k], head_w_tm[32][head_k], da NULL, stage 4 only): da is recomputed from the head's dlogits.
+ * out_of_place: dy goes to its own buffer instead of over da.  Out: sums[2*c] = (sum dz*xhat, sum dz), dgamma, dbeta [c], coef[3*c]
+ * (NaN where no stage wrote them), dy[pixels][c], *ticket (tables), *workgroups of the reduce. */
+typedef struct {
+    int c, head_k; int64_t pixels;
+    const float* da; const float* y; const float* gamma; const float* mean; const float* invstd; const float* scale; const float* shift;
+    const float* head_g; const float* head_w_tm; const float* coef_in;
+    int tables, out_of_place, stages;
+    double* sums; float* dgamma; float* dbeta; float* coef; float* dy;
+    int64_t ticket; int workgroups;
+} anh_op_bn_bwd;
+int anh_op_bn_backward(int precision, anh_op_bn_bwd* op);
+
+/* The fused tail of a training step (1x1 head on 32 channels, k <= 4 classes: logits, weighted softmax log-loss, head backward-data,
+ * filter and bias gradient) in one launch.  a (and b: skip sum) as anh_op_bn_input; w_tm[32][k]; labels (ANH_LABEL_IGNORE = none).
+ * da_virtual: da is not stored, dlogits is.  bn_sums: 0 none, 1 per-workgroup partials, 2 table + finish (needs a in table form) — the
+ * bn + relu backward sums of a's layer (single input only), with bn_mean / bn_invstd (partials form) and bn_gamma (finish).
+ * fold_jobs: bn layers whose fold rides in the launch's first workgroups.  Out: logits, dlogits [pixels][k], da[pixels][32], loss,
+ * dbias[k], dw[32][k], bn_sums_out[64] = (sum dz*xhat, sum dz), dgamma, dbeta [32], coef[96] (NaN unless the finish ran), error_flag. */
+typedef struct {
+    int k; int64_t pixels; double scale;
+    const anh_op_bn_input* a; const anh_op_bn_input* b;
+    const float* w_tm; const float* bias; const uint16_t* labels; const float* weights;
+    int da_virtual, bn_sums;
+    const float* bn_mean; const float* bn_invstd; const float* bn_gamma;
+    anh_op_bn_layer* fold_jobs; int n_fold_jobs;
+    float* logits; float* dlogits; float* da; double* loss; float* dbias; float* dw;
+    double* bn_sums_out; float* dgamma; float* dbeta; float* coef;
+    int error_flag; int64_t ticket; int workgroups;
+} anh_op_head;
+int anh_op_head_train(int precision, anh_op_head* op);
+/* the unfused loss kernel on fp32 logits[pixels][k], k <= 64 */
+int anh_op_loss(const float* logits, const uint16_t* labels, const float* weights, int64_t pixels, int k, double scale,
+                float* dlogits, double* loss, float* dbias, int* error_flag);
+
 /* ---- host logic ---- */
 /* tiling::get_tiles(width, height, params) (annonet_infer.cpp:42): *tiles is malloc'd, release with anh_free */
 int anh_get_tiles(int width, int height, const anh_tiling_params* params, anh_tile** tiles, size_t* count);

@@ -4,8 +4,12 @@ process), so that every workgroup walks many (pixel tile, slab) items: ring buff
 grid-stride walk (grid 3) both run, the producer-issued stores / sums of "two items ago" and the tile-ahead old-value prefetch
 reach their steady state.  The bars are those of test_gpu_ops.py (one bf16 ulp on <= 2 % of the elements against orc_op_*; filter
 gradients rtol 2e-3; fused sums 2e-5 / 1e-4 of float64 sums over the stored tensor) — the functions themselves are reused.
+The table forms of the conv epilogues and prologues (tests/test_gpu_train_ops.py) run in the same loop: with 3 and 8 workgroups the
+replica choice and the finish's ticket run with fewer workgroups than a table has replicas.
+"loops" is the same idea for the kernels that are not convolutions: the process sets ANH_HEAD_BLOCKS / ANH_APPLY_BLOCKS to 2, so every
+thread of the fused head and of the bn backward apply passes walks many pixels of a 4099-pixel tensor.
 
-usage: run_ops_regime.py [small|full]      prints one line per case, exits 1 if any case failed
+usage: run_ops_regime.py [small|full|loops]      prints one line per case, exits 1 if any case failed
 """
 import os
 import sys
@@ -19,6 +23,7 @@ import numpy as np  # noqa: E402
 
 import annonet_amd as aa  # noqa: E402
 import test_gpu_ops as ops  # noqa: E402
+import test_gpu_train_ops as tops  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 
 BF = aa.ANH_BF16
@@ -59,8 +64,26 @@ def must_be_mfma(desc, n, h, w):
     assert mf, ("not on the MFMA kernels", desc)
 
 
+def loops():
+    bad = 0
+    for K in (1, 2, 3, 4):
+        for precision in (aa.ANH_FP32, BF):
+            for skip in (False, True):
+                bad += run("fused head K=%d skip=%d precision=%d" % (K, skip, precision), tops.test_head_train, K, 4099, skip, precision)
+            bad += run("bn backward apply, head form K=%d precision=%d" % (K, precision), tops.test_bn_backward_apply_recomputes_da_from_the_dlogits, K, 4099, precision)
+        bad += run("fused head with bn sums K=%d" % K, tops.test_head_train_bn_sums_in_all_three_forms, K, 4099)
+    for c in (8, 24, 32, 40, 64, 128, 256):
+        for precision in (aa.ANH_FP32, BF):
+            bad += run("bn backward c=%d precision=%d" % (c, precision), tops.test_bn_backward, c, 4099, precision)
+    return bad
+
+
 def main():
     which = sys.argv[1] if len(sys.argv) > 1 else "small"
+    if which == "loops":
+        bad = loops()
+        print("failed cases: %d" % bad, flush=True)
+        sys.exit(1 if bad else 0)
     shapes = REGIME if which == "small" else FULL
     bad = 0
     for desc, n, h, w in shapes:
@@ -75,6 +98,11 @@ def main():
             bad += run("forward + bn statistics p%d %s" % (prologue, tag), ops.test_conv_forward_fused_bn_statistics, desc, n, h, w, prologue)
         for accumulate in (False, True):
             bad += run("backward-data + bn sums acc=%d %s" % (accumulate, tag), ops.test_conv_backward_data_fused_bn_reduction, desc, n, h, w, accumulate)
+        for prologue in (1, 2):
+            bad += run("forward into a table p%d %s" % (prologue, tag), tops.test_conv_forward_into_a_table, desc, n, h, w, prologue)
+            bad += run("forward folding its producers' tables p%d %s" % (prologue, tag), tops.test_conv_prologue_folds_its_producers_tables, desc, n, h, w, prologue)
+        for accumulate in (False, True):
+            bad += run("backward-data + table sums + finish acc=%d %s" % (accumulate, tag), tops.test_conv_backward_data_with_table_sums_and_finish, desc, n, h, w, accumulate)
     if which == "small":
         # the stem kernels are persistent too (ANH_STEM_BLOCKS / ANH_STEM_WGRAD_BLOCKS)
         stem = ((0, 5, 1, 2, 3, 32), 3, 45, 70)
@@ -82,6 +110,7 @@ def main():
             bad += run("stem forward", ops.test_conv_forward, *stem, prologue, BF)
         bad += run("stem filter gradient with dy in the kernel", ops.test_stem_filter_gradient_computes_dy_in_kernel)
         bad += run("stem filter gradient", ops.test_conv_backward_filter, *stem, 0, BF)
+        bad += run("stem forward into a table", tops.test_stem_forward_into_a_table, stem)
     print("failed cases: %d" % bad, flush=True)
     sys.exit(1 if bad else 0)
 

@@ -337,7 +337,8 @@ def test_bf16_training_step(levels, scaler, minf, in_ch):
     assert abs(got_loss - fp32_loss) <= 0.03 * max(1.0, abs(fp32_loss))
     # Whole-net gradients can only be held to a loose bar in bf16: two correct implementations decorrelate at the level
     # of one bf16 ulp (summation order moves dbeta by ~0.3%, which shifts every dy and re-rolls every rounding), and that
-    # compounds through each bn backward.  Kernel-exact checks with identical inputs live in test_gpu_ops.py.
+    # compounds through each bn backward.  Kernel-exact checks with identical inputs live in test_gpu_ops.py (convolutions) and
+    # test_gpu_train_ops.py: dgamma / dbeta / coef of every bn layer (exact from the table totals), dy, the head's dW / db / loss.
     g, gw = t.get_grads(), o.grads
     for li, L in enumerate(o.layers):
         nw = L.k * L.k * L.cin * L.cout
