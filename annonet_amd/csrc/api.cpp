@@ -2,6 +2,7 @@
 // status code and leaves the message in a thread-local string (anh_last_error).
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -21,14 +22,6 @@ using namespace anh;
 
 namespace {
 thread_local std::string g_error;
-
-template <typename F>
-int guarded(F&& f) {
-    try { f(); return ANH_OK; }
-    catch (const Error& e) { g_error = e.what(); return e.code; }
-    catch (const std::bad_alloc&) { g_error = "host allocation failed"; return ANH_ERR_OOM; }
-    catch (const std::exception& e) { g_error = e.what(); return ANH_ERR_INTERNAL; }
-}
 
 const char kRuntimeMagic[8] = {'A', 'N', 'H', 'R', 'T', '0', '0', '1'};
 const char kStateMagic[8] = {'A', 'N', 'H', 'T', 'S', '0', '0', '2'};   // 002: + bn update counters, schedule counter, unrecorded losses
@@ -76,61 +69,33 @@ void wait_stream(hipStream_t st, bool bounded) {
 }
 }  // namespace anh
 
-// ANH_REPLICA_WORKERS=0: round 3's form (threads created and joined on every call) for the before / after figure of DESIGN.md §6
-static bool persistent_workers() { static const bool on = !(getenv("ANH_REPLICA_WORKERS") && atoi(getenv("ANH_REPLICA_WORKERS")) == 0); return on; }
-
 struct anh_runtime {
-    std::unique_ptr<Engine> eng;          // replica 0 (the only one unless anh_set_devices named several devices)
-    // anh_set_devices: one process drives several GPUs.  Replica r lives on devices[r]; every replica holds the same weights;
-    // annonet_infer() shards its tile list over them (infer_multi below).  Empty list = the creating thread's current device.
-    std::vector<int> devices;
-    struct Replica { std::unique_ptr<Engine> eng; };
-    std::vector<Replica> extra;           // replicas 1 .. R-1
-    std::unique_ptr<Collective> coll;
-    std::unique_ptr<ReplicaWorkers> workers;   // persistent host threads, one per replica beyond the first (multidev.h)
-    template <class F> void each_replica(F&& fn) { if (workers && persistent_workers()) workers->run(fn); else for_each_replica(replicas(), fn); }
     struct Exchange { DevBuf packed, rects, offsets; };
     std::vector<Exchange> exchange;       // per replica: scratch of the overlap exchange
-    size_t replicas() const { return 1 + extra.size(); }
-    int device_of(size_t r) const { return devices.empty() ? -1 : devices[r]; }
-    Engine& replica(size_t r) { return r == 0 ? *eng : *extra[r - 1].eng; }
     // `only_device` >= 0: ONE replica on that device whatever anh_set_devices named (a trainer's snapshot, below)
     void build(const anh_net_config& cfg, int only_device = -1) {
-        devices = selected_devices();
-        if (only_device >= 0) devices.assign(1, only_device);
-        { DeviceScope scope(device_of(0)); eng = std::make_unique<Engine>(cfg, false); }
-        for (size_t r = 1; r < devices.size(); ++r) { DeviceScope scope(devices[r]); extra.push_back(Replica{std::make_unique<Engine>(cfg, false)}); }
-        if (devices.size() > 1) { coll = std::make_unique<Collective>(devices); workers = std::make_unique<ReplicaWorkers>(devices); }
-        for (size_t r = 0; r < replicas(); ++r) replica(r).bounded_waits = replicas() > 1;   // host waits with a deadline (common.h)
-        exchange.resize(replicas());
+        reps.build(only_device >= 0 ? std::vector<int>(1, only_device) : selected_devices(), cfg, false, nullptr);
+        exchange = std::vector<Exchange>(reps.size());
     }
     void set_params_all(const float* params, const float* running) {
-        for (size_t r = 0; r < replicas(); ++r) { DeviceScope scope(device_of(r)); replica(r).set_params(params, running); }
+        reps.for_all([&](size_t, Engine& e) { e.set_params(params, running); });
     }
     // host-buffer annonet_infer(): image strips go up and label strips come down through small pinned rings while the tiles
     // compute, so that neither transfer is exposed (anh_infer below)
     static constexpr int kRing = 3;
-    struct Pinned { void* p = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; bool busy = false; };
+    struct Pinned { PinnedBuf mem; Event done; bool busy = false; };
     Pinned up[kRing], down[kRing];
-    hipStream_t copy_up = nullptr, copy_down = nullptr;
-    std::vector<hipEvent_t> strip_events;
-    ~anh_runtime() {
-        for (auto* ring : {up, down})
-            for (int i = 0; i < kRing; ++i) {
-                if (ring[i].p) (void)hipHostFree(ring[i].p);
-                if (ring[i].done) (void)hipEventDestroy(ring[i].done);
-            }
-        for (auto ev : strip_events) (void)hipEventDestroy(ev);
-        if (copy_up) (void)hipStreamDestroy(copy_up);
-        if (copy_down) (void)hipStreamDestroy(copy_down);
-        for (size_t r = extra.size(); r-- > 0;) { DeviceScope scope(device_of(r + 1)); extra[r].eng.reset(); exchange[r + 1] = Exchange{}; }
-    }
+    Stream copy_up, copy_down;
+    std::vector<Event> strip_events;
+    Event labels_ready;   // a strip of the label map is final on the compute stream
+    // anh_set_devices: one process drives several GPUs.  Every replica holds the same weights; annonet_infer() shards its tile list
+    // over them (infer_multi below).  The last member: the engines drain and die before anything above is released.
+    ReplicaSet reps;
 };
 
 struct anh_trainer {
     anh_net_config cfg{2, 3, 3, 1.0, 1, ANH_BF16};
     uint64_t seed = 0;
-    std::unique_ptr<Engine> eng;
     LrSchedule sched;
     double weight_decay = 0.0005, momentum = 0.9;
     unsigned long bn_window = 100;
@@ -146,7 +111,7 @@ struct anh_trainer {
     // job (who all see the same all-reduced loss) shrink their rate at the same step.
     static constexpr unsigned long kLossLag = 4;
     // pinned ring of posted losses: the update kernel of step k stores (tag(k) << 32 | float bits) into slot k mod 256 (SgdArgs::loss_post)
-    unsigned long long* loss_ring = nullptr;      // host address
+    PinnedBuf loss_ring;
     unsigned long long* loss_ring_dev = nullptr;  // the same words as the device sees them
     static unsigned int loss_tag(unsigned long step) { return (unsigned int)(step & 0x7fffffffu) | 0x80000000u; }   // never the 0 of a fresh slot
     struct PendingLoss { int slot; unsigned long step; bool arrived; double value; };
@@ -158,70 +123,45 @@ struct anh_trainer {
     // stream and chains the compute behind the upload with events; the call returns once the inputs are packed
     // (annonet_train_main.cpp:585-586 refills samples/labels right after StartTraining returns).
     struct StageSet {
-        void* pinned = nullptr; size_t pinned_bytes = 0;
+        PinnedBuf pinned;
         DevBuf dev;
-        hipEvent_t uploaded = nullptr, consumed = nullptr;   // H2D of this set done / the step that read it has finished
+        Event uploaded, consumed;   // H2D of this set done / the step that read it has finished
         bool in_flight = false;
         double wait_us = 0;   // how long the last call that packed into this set waited for the GPU to release it
     };
-    StageSet stage[2];
-    hipStream_t copy_stream = nullptr;
+    // per replica, sized once when the handle is created (a set is never moved while its upload is in flight)
+    std::vector<std::array<StageSet, 2>> stage;
+    std::vector<Stream> copy_stream;
     unsigned long host_steps = 0;
-    // anh_set_devices: data-parallel training from ONE process (annonet_train_main.cpp:583-614 stays as it is).  Replica r lives on
-    // devices[r] with its own staging sets; StartTraining splits the mini-batch along N, one all-reduce (RCCL) sums the flat
-    // gradient buckets, every replica applies the identical update.  Batch-norm statistics are per replica.
-    std::vector<int> devices;
-    struct Replica { std::unique_ptr<Engine> eng; StageSet stage[2]; hipStream_t copy_stream = nullptr; };
-    std::vector<std::unique_ptr<Replica>> extra;   // replicas 1 .. R-1
-    std::unique_ptr<Collective> coll;
-    std::unique_ptr<ReplicaWorkers> workers;       // persistent host threads, one per replica beyond the first (multidev.h)
-    template <class F> void each_replica(F&& fn) { if (workers && persistent_workers()) workers->run(fn); else for_each_replica(replicas(), fn); }
     // what one StartTraining costs the host, and the exchange step on the device (anh_trainer_exchange_stats): host time of every call;
     // on every `xs_every`-th step an event pair around each part of the all-reduce on replica 0's streams (ANH_EXCHANGE_SAMPLE, default 8, 0 = never)
     struct ExchangeStats {
         int64_t calls = 0; double host_us_sum = 0, host_us_last = 0, wait_us_sum = 0;
         uint64_t worker_calls_base = 0;
-        hipEvent_t tail0 = nullptr, tail1 = nullptr, head0 = nullptr, head1 = nullptr;
+        Event tail0, tail1, head0, head1;
         bool pending = false, split = false;
         int64_t samples = 0; double tail_us_sum = 0, head_us_sum = 0, tail_us_last = 0, head_us_last = 0;
     } xs;
     void collect_exchange_sample() {   // the pair of a sampled step, once that step has finished (blocks until then)
         if (!xs.pending) return;
-        DeviceScope scope(device_of(0));
+        DeviceScope scope(reps.device_of(0));
         float ms = 0;
-        HIP_CHECK(hipEventSynchronize(xs.head1));
-        HIP_CHECK(hipEventElapsedTime(&ms, xs.head0, xs.head1));
+        HIP_CHECK(hipEventSynchronize(xs.head1.get()));
+        HIP_CHECK(hipEventElapsedTime(&ms, xs.head0.get(), xs.head1.get()));
         xs.head_us_last = 1e3 * ms; xs.head_us_sum += xs.head_us_last;
         xs.tail_us_last = 0;
-        if (xs.split) { HIP_CHECK(hipEventSynchronize(xs.tail1)); HIP_CHECK(hipEventElapsedTime(&ms, xs.tail0, xs.tail1)); xs.tail_us_last = 1e3 * ms; xs.tail_us_sum += xs.tail_us_last; }
+        if (xs.split) { HIP_CHECK(hipEventSynchronize(xs.tail1.get())); HIP_CHECK(hipEventElapsedTime(&ms, xs.tail0.get(), xs.tail1.get())); xs.tail_us_last = 1e3 * ms; xs.tail_us_sum += xs.tail_us_last; }
         ++xs.samples;
         xs.pending = false;
     }
-    size_t replicas() const { return devices.size() > 1 ? devices.size() : 1; }
-    int device_of(size_t r) const { return devices.empty() ? -1 : devices[r]; }
-    Engine& replica(size_t r) { return r == 0 ? *eng : *extra[r - 1]->eng; }
-    StageSet* stage_of(size_t r) { return r == 0 ? stage : extra[r - 1]->stage; }
-    hipStream_t& copy_stream_of(size_t r) { return r == 0 ? copy_stream : extra[r - 1]->copy_stream; }
-
     bool initialized = false, dirty = false;
     // The reference configures AFTER Initialize() (annonet_train_main.cpp:400-410: Initialize, SetNetWidth, ..., SetClassCount);
     // dlib allocates lazily, so the net is (re)built here on first use after a structural setting changed.
     Engine& engine() {
         if (!initialized) fail(ANH_ERR_INVALID, "TrainingNet::Initialize has not been called");
-        if (!eng || dirty) {
+        if (!reps.built() || dirty) {
             if (steps > 0) fail(ANH_ERR_INVALID, "the net structure cannot change once training has started");
-            { DeviceScope scope(device_of(0)); eng = std::make_unique<Engine>(cfg, true); eng->random_init(seed); }
-            extra.clear();
-            for (size_t r = 1; r < replicas(); ++r) {   // same seed: every replica starts from the same weights
-                DeviceScope scope(device_of(r));
-                auto rep = std::make_unique<Replica>();
-                rep->eng = std::make_unique<Engine>(cfg, true);
-                rep->eng->random_init(seed);
-                extra.push_back(std::move(rep));
-            }
-            if (replicas() > 1 && !coll) coll = std::make_unique<Collective>(devices);
-            if (replicas() > 1 && !workers) workers = std::make_unique<ReplicaWorkers>(devices);
-            for (size_t r = 0; r < replicas(); ++r) replica(r).bounded_waits = replicas() > 1;   // host waits with a deadline (common.h)
+            reps.build(reps.devices, cfg, true, &seed);   // same seed: every replica starts from the same weights
             dirty = false;
         }
         if (resume_pending) {   // the reference names the file BEFORE SetClassCount (annonet_train_main.cpp:400-405): resume on first use
@@ -232,18 +172,18 @@ struct anh_trainer {
             if (probe.good()) { probe.close(); resume(); }
             resume_pending = false;
         }
-        return *eng;
+        return reps.engine(0);
     }
     void resume();
     void structural_change() { if (steps > 0) fail(ANH_ERR_INVALID, "the net structure cannot change once training has started"); dirty = true; }
     void arrive(PendingLoss& p) {   // blocks until the loss of that step is on the host
         if (p.arrived) return;
-        const volatile unsigned long long* word = loss_ring + p.slot;
+        const volatile unsigned long long* word = loss_ring.as<unsigned long long>() + p.slot;
         const unsigned int want = loss_tag(p.step);
         unsigned long long w = *word;
         if ((unsigned int)(w >> 32) != want) {
             // not there yet: the stream is at most kLossLag steps behind.  Drain it (this also surfaces a device fault) and look again.
-            { DeviceScope scope(device_of(0)); eng->synchronize(); }
+            { DeviceScope scope(reps.device_of(0)); reps.engine(0).synchronize(); }
             w = *word;
             if ((unsigned int)(w >> 32) != want) fail(ANH_ERR_INTERNAL, "the loss of a finished step was not posted");
         }
@@ -266,29 +206,11 @@ struct anh_trainer {
         for (auto& p : pending) arrive(p);
         if (!pending.empty()) last_loss = pending.back().value;
     }
-    ~anh_trainer() {
-        workers.reset();   // the worker threads first: nothing of theirs outlives the replicas
-        for (hipEvent_t ev : {xs.tail0, xs.tail1, xs.head0, xs.head1}) if (ev) (void)hipEventDestroy(ev);
-        if (loss_ring) (void)hipHostFree(loss_ring);
-        for (auto& st : stage) {
-            if (st.pinned) (void)hipHostFree(st.pinned);
-            if (st.uploaded) (void)hipEventDestroy(st.uploaded);
-            if (st.consumed) (void)hipEventDestroy(st.consumed);
-        }
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
-        for (size_t r = extra.size(); r-- > 0;) {
-            DeviceScope scope(device_of(r + 1));
-            Replica& rep = *extra[r];
-            rep.eng.reset();
-            for (auto& st : rep.stage) {
-                st.dev.release();
-                if (st.pinned) (void)hipHostFree(st.pinned);
-                if (st.uploaded) (void)hipEventDestroy(st.uploaded);
-                if (st.consumed) (void)hipEventDestroy(st.consumed);
-            }
-            if (rep.copy_stream) (void)hipStreamDestroy(rep.copy_stream);
-        }
-    }
+    // anh_set_devices: data-parallel training from ONE process (annonet_train_main.cpp:583-614 stays as it is).  Replica r has its
+    // own staging sets; StartTraining splits the mini-batch along N, one all-reduce (RCCL) sums the flat gradient buckets, every
+    // replica applies the identical update.  Batch-norm statistics are per replica.  The last member: the engines
+    // drain and die before the staging sets, the loss ring and the events above are released.
+    ReplicaSet reps;
 };
 
 // Full images of a dataset, resident in HBM, plus the scratch of the device crop path.
@@ -298,14 +220,11 @@ struct anh_dataset {
     std::vector<Item> items;          // a removed image leaves an empty slot (height 0) that a later add reuses
     std::vector<int> free_slots;
     uint64_t resident_bytes = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
     DevBuf d_specs, d_hist, d_first, d_table, d_bad;
-    void* pinned = nullptr; size_t pinned_bytes = 0;
+    PinnedBuf pinned;
     DevBuf out;   // outputs of the host-array form
-    ~anh_dataset() {
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-        if (pinned) (void)hipHostFree(pinned);
-    }
+    ~anh_dataset() { if (stream.get()) (void)hipStreamSynchronize(stream.get()); }
     // Cuts n crops into device arrays on `stream`.  One host round trip inside: the per-crop label histograms come back,
     // set_weights' table is computed with the host's own arithmetic (bit-identical to set_weights on the crop) and goes up.
     void crop_batch(const anh_crop_spec* specs, int n, int dim, int classes, double cw, double iw, uint8_t* d_images, uint16_t* d_labels, float* d_weights) {
@@ -313,15 +232,10 @@ struct anh_dataset {
         ANH_REQUIRE(classes >= 1 && classes <= kCropMaxClasses, "crop batch: class count must be 1..64");
         const size_t spec_bytes = (size_t)n * sizeof(CropSource), tab = (size_t)n * kCropMaxClasses * 4;
         const size_t need = spec_bytes + 3 * tab + 64;
-        if (need > pinned_bytes) {
-            HIP_CHECK(hipStreamSynchronize(stream));
-            if (pinned) HIP_CHECK(hipHostFree(pinned));
-            pinned = nullptr; pinned_bytes = 0;
-            HIP_CHECK(hipHostMalloc(&pinned, need, hipHostMallocDefault));
-            pinned_bytes = need;
-        }
+        const hipStream_t st = stream.get();
+        if (need > pinned.bytes) { HIP_CHECK(hipStreamSynchronize(st)); pinned.reserve(need); }
         d_specs.reserve(spec_bytes); d_hist.reserve(tab); d_first.reserve(tab); d_table.reserve(tab); d_bad.reserve(4);
-        char* pin = static_cast<char*>(pinned);
+        char* pin = pinned.as<char>();
         CropSource* hs = reinterpret_cast<CropSource*>(pin);
         unsigned* h_hist = reinterpret_cast<unsigned*>(pin + spec_bytes);
         unsigned* h_first = reinterpret_cast<unsigned*>(pin + spec_bytes + tab);
@@ -341,21 +255,49 @@ struct anh_dataset {
                                c.flip_left_right ? 1 : 0, c.flip_upside_down ? 1 : 0, c.brightness_change, src_dim, c.noise_level,
                                (unsigned long long)c.noise_seed, {c.color_offset[0], c.color_offset[1], c.color_offset[2]}};
         }
-        HIP_CHECK(hipMemcpyAsync(d_specs.p, hs, spec_bytes, hipMemcpyHostToDevice, stream));
-        HIP_CHECK(hipMemsetAsync(d_bad.p, 0, 4, stream));
-        launch_crop_pixels(d_specs.as<CropSource>(), n, dim, channels, d_images, d_labels, d_hist.as<unsigned>(), d_first.as<unsigned>(), d_bad.as<int>(), classes, stream);
-        HIP_CHECK(hipMemcpyAsync(h_hist, d_hist.p, tab, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipMemcpyAsync(h_first, d_first.p, tab, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipMemcpyAsync(h_bad, d_bad.p, 4, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
+        HIP_CHECK(hipMemcpyAsync(d_specs.p, hs, spec_bytes, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemsetAsync(d_bad.p, 0, 4, st));
+        launch_crop_pixels(d_specs.as<CropSource>(), n, dim, channels, d_images, d_labels, d_hist.as<unsigned>(), d_first.as<unsigned>(), d_bad.as<int>(), classes, st);
+        HIP_CHECK(hipMemcpyAsync(h_hist, d_hist.p, tab, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h_first, d_first.p, tab, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h_bad, d_bad.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
         ANH_REQUIRE(*h_bad == 0, "label value exceeds the class count");
         for (int i = 0; i < n; ++i)
             set_weights_table(h_hist + (size_t)i * kCropMaxClasses, h_first + (size_t)i * kCropMaxClasses, kCropMaxClasses, (long long)dim * dim, cw, iw,
                               h_table + (size_t)i * kCropMaxClasses);
-        HIP_CHECK(hipMemcpyAsync(d_table.p, h_table, tab, hipMemcpyHostToDevice, stream));
-        launch_crop_weights(d_labels, d_table.as<float>(), n, dim, d_weights, stream);
+        HIP_CHECK(hipMemcpyAsync(d_table.p, h_table, tab, hipMemcpyHostToDevice, st));
+        launch_crop_weights(d_labels, d_table.as<float>(), n, dim, d_weights, st);
     }
 };
+
+namespace {
+// [images | labels u16 | weights f32] of n samples in ONE block (a staging set, the crops of a batch): each part starts on a 256-byte boundary
+struct BatchLayout {
+    size_t img_bytes, lab_off, w_off, total;
+    BatchLayout(size_t n, size_t plane, int channels)
+        : img_bytes(n * plane * channels), lab_off((img_bytes + 255) / 256 * 256), w_off((lab_off + n * plane * 2 + 255) / 256 * 256), total(w_off + n * plane * 4) {}
+    uint16_t* labels(void* base) const { return reinterpret_cast<uint16_t*>(static_cast<char*>(base) + lab_off); }
+    float* weights(void* base) const { return reinterpret_cast<float*>(static_cast<char*>(base) + w_off); }
+};
+
+bool detection_requested(const double* detection_levels, int K) {
+    bool any = false;
+    if (detection_levels) for (int k = 0; k < K; ++k) { ANH_REQUIRE(detection_levels[k] >= 0.0, "detection levels must be >= 0"); if (detection_levels[k] > 0.0) any = true; }
+    return any;
+}
+// detection-level filter (annonet_infer.cpp:187-239), on the resident planes (stage_blended) and label map (stage_result) of h x w.
+// Seeds are looked up at (row, col): the reference stores (r, c) but reads (point.y(), point.x()) — transposed (:210 vs :222); see DESIGN.md.
+void apply_detection_levels(Engine& e, const double* levels, int K, int h, int w) {
+    const size_t plane = (size_t)h * w;
+    e.stage_out.reserve(plane + (size_t)K * sizeof(double) + 64);
+    uint8_t* flags = e.stage_out.as<uint8_t>();
+    double* d_det = reinterpret_cast<double*>(flags + ((plane + 15) / 16) * 16);
+    int* d_changed = reinterpret_cast<int*>(d_det + K);
+    HIP_CHECK(hipMemcpyAsync(d_det, levels, (size_t)K * sizeof(double), hipMemcpyHostToDevice, e.stream));
+    run_detection_filter(e.stage_blended.as<float>(), e.stage_result.as<uint16_t>(), K, h, w, d_det, flags, d_changed, e.stream);
+}
+}  // namespace
 
 extern "C" {
 
@@ -375,7 +317,7 @@ int anh_set_devices(const int* devices, int n) {
 }
 int anh_handle_replicas(void* handle, int is_trainer) {
     if (!handle) return 0;
-    return is_trainer ? (int)((anh_trainer*)handle)->replicas() : (int)((anh_runtime*)handle)->replicas();
+    return (int)(is_trainer ? ((anh_trainer*)handle)->reps : ((anh_runtime*)handle)->reps).size();
 }
 int anh_host_register(void* p, size_t bytes) {
     return guarded([&] { ANH_REQUIRE(p && bytes, "host register: null block"); HIP_CHECK(hipHostRegister(p, bytes, hipHostRegisterDefault)); });
@@ -454,28 +396,28 @@ int anh_runtime_create(const anh_net_config* cfg, anh_runtime** out) {
 }
 void anh_runtime_destroy(anh_runtime* h) { delete h; }
 int anh_runtime_config(const anh_runtime* h, anh_net_config* out) {
-    return guarded([&] { ANH_REQUIRE(h && out, "null argument"); *out = h->eng->spec.cfg; });
+    return guarded([&] { ANH_REQUIRE(h && out, "null argument"); *out = h->reps.engine(0).spec.cfg; });
 }
 int anh_runtime_set_params(anh_runtime* h, const float* params, int64_t n_params, const float* running, int64_t n_running) {
     return guarded([&] {
         ANH_REQUIRE(h && params && running, "null argument");
-        ANH_REQUIRE(n_params == h->eng->spec.n_params && n_running == h->eng->spec.n_running, "parameter blob size mismatch");
+        ANH_REQUIRE(n_params == h->reps.engine(0).spec.n_params && n_running == h->reps.engine(0).spec.n_running, "parameter blob size mismatch");
         h->set_params_all(params, running);
     });
 }
 int anh_runtime_get_params(const anh_runtime* h, float* params, int64_t n_params, float* running, int64_t n_running) {
     return guarded([&] {
         ANH_REQUIRE(h, "null handle");
-        ANH_REQUIRE((!params || n_params == h->eng->spec.n_params) && (!running || n_running == h->eng->spec.n_running), "parameter blob size mismatch");
-        DeviceScope scope(h->device_of(0));
-        h->eng->get_params(params, running);
+        ANH_REQUIRE((!params || n_params == h->reps.engine(0).spec.n_params) && (!running || n_running == h->reps.engine(0).spec.n_running), "parameter blob size mismatch");
+        DeviceScope scope(h->reps.device_of(0));
+        h->reps.engine(0).get_params(params, running);
     });
 }
 int anh_runtime_serialize(const anh_runtime* h, void** blob, size_t* size) {
     return guarded([&] {
         ANH_REQUIRE(h && blob && size, "null argument");
-        DeviceScope scope(h->device_of(0));
-        const Spec& s = h->eng->spec;
+        DeviceScope scope(h->reps.device_of(0));
+        const Spec& s = h->reps.engine(0).spec;
         const size_t bytes = sizeof(BlobHeader) + (size_t)(s.n_params + s.n_running) * 4;
         char* p = (char*)std::malloc(bytes);
         if (!p) fail(ANH_ERR_OOM, "host allocation failed");
@@ -484,7 +426,7 @@ int anh_runtime_serialize(const anh_runtime* h, void** blob, size_t* size) {
         hd.levels = s.cfg.levels; hd.in_channels = s.cfg.in_channels; hd.classes = s.cfg.classes; hd.min_filters = s.cfg.min_filters;
         hd.width_scaler = s.cfg.width_scaler; hd.n_params = s.n_params; hd.n_running = s.n_running;
         std::memcpy(p, &hd, sizeof hd);
-        try { h->eng->get_params((float*)(p + sizeof hd), (float*)(p + sizeof hd) + s.n_params); }
+        try { h->reps.engine(0).get_params((float*)(p + sizeof hd), (float*)(p + sizeof hd) + s.n_params); }
         catch (...) { std::free(p); throw; }
         *blob = p; *size = bytes;
     });
@@ -511,11 +453,9 @@ int anh_runtime_deserialize(const void* blob, size_t size, int precision, anh_ru
 int anh_runtime_forward_device(anh_runtime* h, const uint8_t* d_image, int n, int height, int width, float* d_out_nchw) {
     return guarded([&] {
         ANH_REQUIRE(h && d_image && d_out_nchw, "null argument");
-        DeviceScope scope(h->device_of(0));
-        Src img;
-        img.kind = SRC_IMAGE; img.img = d_image; img.img_h = height; img.img_w = width;
-        img.img_sample_stride = (int64_t)height * width * h->eng->spec.cfg.in_channels;
-        h->eng->forward_inference(img, n, height, width, d_out_nchw);
+        DeviceScope scope(h->reps.device_of(0));
+        Engine& e = h->reps.engine(0);
+        e.forward_inference(image_source(d_image, height, width, e.spec.cfg.in_channels), n, height, width, d_out_nchw);
     });
 }
 
@@ -523,17 +463,14 @@ int anh_runtime_forward(anh_runtime* h, const uint8_t* image, int n, int height,
     return guarded([&] {
         ANH_REQUIRE(h && image && out, "null argument");
         ANH_REQUIRE(n >= 1 && height >= 1 && width >= 1, "empty input");
-        DeviceScope scope(h->device_of(0));
-        Engine& e = *h->eng;
+        DeviceScope scope(h->reps.device_of(0));
+        Engine& e = h->reps.engine(0);
         const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
         const size_t in_bytes = (size_t)n * height * width * C, out_elems = (size_t)n * K * height * width;
         e.stage_image.reserve(in_bytes);
         e.stage_out.reserve(out_elems * 4);
         HIP_CHECK(hipMemcpyAsync(e.stage_image.p, image, in_bytes, hipMemcpyHostToDevice, e.stream));
-        Src img;
-        img.kind = SRC_IMAGE; img.img = e.stage_image.as<uint8_t>(); img.img_h = height; img.img_w = width;
-        img.img_sample_stride = (int64_t)height * width * C;
-        e.forward_inference(img, n, height, width, e.stage_out.as<float>());
+        e.forward_inference(image_source(e.stage_image.as<uint8_t>(), height, width, C), n, height, width, e.stage_out.as<float>());
         e.host_out.resize(out_elems);
         HIP_CHECK(hipMemcpyAsync(e.host_out.data(), e.stage_out.p, out_elems * 4, hipMemcpyDeviceToHost, e.stream));
         e.synchronize();
@@ -556,14 +493,14 @@ int anh_infer_device(anh_runtime* h, const uint8_t* d_image, int height, int wid
                      const anh_tile* tiles, size_t n_tiles, uint16_t* d_result, float* d_blended) {
     return guarded([&] {
         ANH_REQUIRE(h && d_image && d_blended, "null argument");
-        DeviceScope scope(h->device_of(0));
+        DeviceScope scope(h->reps.device_of(0));
         std::vector<anh_tile> list = tiles ? std::vector<anh_tile>(tiles, tiles + n_tiles) : tiles_for(tiling, width, height);
         bool whole = tiles == nullptr;
         if (tiles && tiling) {   // a one-rank job hands over its "share": the complete tiling
             const std::vector<anh_tile> all = tiles_for(tiling, width, height);
             whole = all.size() == list.size() && std::memcmp(all.data(), list.data(), all.size() * sizeof(anh_tile)) == 0;
         }
-        h->eng->infer_device(d_image, height, width, gains, list, d_result, d_blended, whole);
+        h->reps.engine(0).infer_device(d_image, height, width, gains, list, d_result, d_blended, whole);
     });
 }
 
@@ -571,39 +508,27 @@ int anh_argmax_device(anh_runtime* h, const float* d_blended, int height, int wi
     return guarded([&] {
         ANH_REQUIRE(h && d_blended && d_result, "null argument");
         ANH_REQUIRE(height >= 1 && width >= 1 && row0 >= 0 && row0 <= row1 && row1 <= height, "argmax: bad row range");
-        DeviceScope scope(h->device_of(0));
-        h->eng->argmax_rows(d_blended, height, width, row0, row1, gains, d_result);
+        DeviceScope scope(h->reps.device_of(0));
+        h->reps.engine(0).argmax_rows(d_blended, height, width, row0, row1, gains, d_result);
     });
 }
 
 namespace {
-void ring_reserve(anh_runtime::Pinned& b, size_t bytes) {
-    if (!b.done) HIP_CHECK(hipEventCreateWithFlags(&b.done, hipEventDisableTiming));
-    if (bytes <= b.bytes) return;
-    if (b.p) HIP_CHECK(hipHostFree(b.p));
-    b.p = nullptr; b.bytes = 0;
-    HIP_CHECK(hipHostMalloc(&b.p, bytes, hipHostMallocDefault));
-    b.bytes = bytes;
-}
+void ring_reserve(anh_runtime::Pinned& b, size_t bytes) { b.done.ensure(); b.mem.reserve(bytes); }
 
 // The streamed form of annonet_infer() for host buffers: the image is uploaded in row strips (host memcpy into a pinned ring
 // -> async DMA on a copy stream), a tile starts as soon as the rows of its window are resident, and the label rows that no
 // later tile can touch are arg-maxed and sent back (pinned ring -> host memcpy) while the next tile row computes.
 void infer_streamed(anh_runtime* h, const uint8_t* image, int H, int W, const double* gains, const std::vector<anh_tile>& tiles, uint16_t* result) {
-    Engine& e = *h->eng;
+    Engine& e = h->reps.engine(0);
     const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
     const size_t plane = (size_t)H * W, row_bytes = (size_t)W * C;
-    if (!h->copy_up) {
-        HIP_CHECK(hipStreamCreateWithFlags(&h->copy_up, hipStreamNonBlocking));
-        HIP_CHECK(hipStreamCreateWithFlags(&h->copy_down, hipStreamNonBlocking));
-    }
+    if (!h->copy_up.get()) { h->copy_up.create(hipStreamNonBlocking); h->copy_down.create(hipStreamNonBlocking); }
+    const hipStream_t copy_up = h->copy_up.get(), copy_down = h->copy_down.get();
+    const hipEvent_t labels_ready = h->labels_ready.ensure();
     const int strip_rows = std::max(1, (int)std::min<size_t>((size_t)H, ((size_t)4 << 20) / std::max<size_t>(row_bytes, 1)));   // ~4 MiB strips
     const int n_strips = (H + strip_rows - 1) / strip_rows;
-    while ((int)h->strip_events.size() < n_strips) {
-        hipEvent_t ev;
-        HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        h->strip_events.push_back(ev);
-    }
+    while ((int)h->strip_events.size() < n_strips) h->strip_events.emplace_back().ensure();
     for (int i = 0; i < anh_runtime::kRing; ++i) { h->up[i].busy = false; h->down[i].busy = false; }
     uint8_t* d_image = e.stage_image.as<uint8_t>();
     float* d_blended = e.stage_blended.as<float>();
@@ -618,12 +543,12 @@ void infer_streamed(anh_runtime* h, const uint8_t* image, int H, int W, const do
             anh_runtime::Pinned& b = h->up[next_strip % anh_runtime::kRing];
             const int r0 = uploaded, r1 = std::min(H, r0 + strip_rows);
             const size_t bytes = (size_t)(r1 - r0) * row_bytes;
-            if (b.busy) HIP_CHECK(hipEventSynchronize(b.done));
+            if (b.busy) HIP_CHECK(hipEventSynchronize(b.done.get()));
             ring_reserve(b, (size_t)strip_rows * row_bytes);
-            std::memcpy(b.p, image + (size_t)r0 * row_bytes, bytes);
-            HIP_CHECK(hipMemcpyAsync(d_image + (size_t)r0 * row_bytes, b.p, bytes, hipMemcpyHostToDevice, h->copy_up));
-            HIP_CHECK(hipEventRecord(b.done, h->copy_up));
-            HIP_CHECK(hipEventRecord(h->strip_events[next_strip], h->copy_up));
+            std::memcpy(b.mem.p, image + (size_t)r0 * row_bytes, bytes);
+            HIP_CHECK(hipMemcpyAsync(d_image + (size_t)r0 * row_bytes, b.mem.p, bytes, hipMemcpyHostToDevice, copy_up));
+            HIP_CHECK(hipEventRecord(b.done.get(), copy_up));
+            HIP_CHECK(hipEventRecord(h->strip_events[next_strip].get(), copy_up));
             b.busy = true;
             uploaded = r1; ++next_strip;
         }
@@ -635,13 +560,11 @@ void infer_streamed(anh_runtime* h, const uint8_t* image, int H, int W, const do
             const Down d = pending.front();
             pending.erase(pending.begin());
             anh_runtime::Pinned& b = h->down[d.slot];
-            HIP_CHECK(hipEventSynchronize(b.done));
-            std::memcpy(result + (size_t)d.r0 * W, b.p, (size_t)(d.r1 - d.r0) * W * 2);
+            HIP_CHECK(hipEventSynchronize(b.done.get()));
+            std::memcpy(result + (size_t)d.r0 * W, b.mem.p, (size_t)(d.r1 - d.r0) * W * 2);
             b.busy = false;
         }
     };
-    hipEvent_t labels_ready;
-    HIP_CHECK(hipEventCreateWithFlags(&labels_ready, hipEventDisableTiming));
     int labels_done = 0, down_slot = 0;
     const size_t max_down_rows = std::min<size_t>((size_t)H, std::max<size_t>(1, ((size_t)16 << 20) / ((size_t)W * 2)));   // label strips of <= 16 MiB
     auto send_labels = [&](int until) {   // rows [labels_done, until) are final on the compute stream
@@ -652,9 +575,9 @@ void infer_streamed(anh_runtime* h, const uint8_t* image, int H, int W, const do
             drain(anh_runtime::kRing - 1);
             anh_runtime::Pinned& b = h->down[down_slot];   // free: at most kRing - 1 strips are pending
             ring_reserve(b, max_down_rows * W * 2);
-            HIP_CHECK(hipStreamWaitEvent(h->copy_down, labels_ready, 0));
-            HIP_CHECK(hipMemcpyAsync(b.p, d_labels + (size_t)r0 * W, (size_t)(r1 - r0) * W * 2, hipMemcpyDeviceToHost, h->copy_down));
-            HIP_CHECK(hipEventRecord(b.done, h->copy_down));
+            HIP_CHECK(hipStreamWaitEvent(copy_down, labels_ready, 0));
+            HIP_CHECK(hipMemcpyAsync(b.mem.p, d_labels + (size_t)r0 * W, (size_t)(r1 - r0) * W * 2, hipMemcpyDeviceToHost, copy_down));
+            HIP_CHECK(hipEventRecord(b.done.get(), copy_down));
             b.busy = true;
             pending.push_back(Down{down_slot, r0, r1});
             down_slot = (down_slot + 1) % anh_runtime::kRing;
@@ -677,7 +600,7 @@ void infer_streamed(anh_runtime* h, const uint8_t* image, int H, int W, const do
             ++j;
         }
         upload_until(need);
-        HIP_CHECK(hipStreamWaitEvent(e.stream, h->strip_events[(need - 1) / strip_rows], 0));
+        HIP_CHECK(hipStreamWaitEvent(e.stream, h->strip_events[(need - 1) / strip_rows].get(), 0));
         e.infer_tiles(&tiles[i], (int)(j - i), d_image, H, W, d_blended);
         upload_until(uploaded + strip_rows * (int)(j - i));   // stay a few strips ahead of the tiles: one more strip per tile enqueued
         if (final_after[j - 1] > labels_done) send_labels(final_after[j - 1]);
@@ -686,7 +609,6 @@ void infer_streamed(anh_runtime* h, const uint8_t* image, int H, int W, const do
     upload_until(H);        // an image larger than its tiles' windows cannot occur, but keep the invariant
     send_labels(H);
     drain(0);
-    HIP_CHECK(hipEventDestroy(labels_ready));
     e.synchronize();
 }
 }  // namespace
@@ -701,17 +623,15 @@ namespace {
 // (the shrunk image is integer-valued and identical everywhere), `image` is unused.
 void infer_multi(anh_runtime* h, const uint8_t* image, int H, int W, const double* gains, const std::vector<anh_tile>& tiles, uint16_t* result, float* blended_out,
                  const uint8_t* original = nullptr, int OH = 0, int OW = 0) {
-    const size_t R = h->replicas();
-    const int K = h->eng->spec.cfg.classes, C = h->eng->spec.cfg.in_channels;
+    const size_t R = h->reps.size();
+    const int K = h->reps.engine(0).spec.cfg.classes, C = h->reps.engine(0).spec.cfg.in_channels;
     const size_t plane = (size_t)H * W;
     const RectTable table = make_rect_table(cross_replica_overlaps(tiles, (int)R, W, H));
     const int64_t total = table.total();
     std::vector<float*> packed(R, nullptr);
     std::vector<hipStream_t> streams(R);
     std::vector<int64_t> lo(R), hi(R);
-    h->each_replica([&](size_t r) {
-        DeviceScope scope(h->device_of(r));
-        Engine& e = h->replica(r);
+    h->reps.each([&](size_t r, Engine& e) {
         shard_range((int64_t)tiles.size(), (int)R, (int)r, lo[r], hi[r]);
         e.stage_image.reserve(plane * C);
         e.stage_blended.reserve(plane * K * 4);
@@ -737,10 +657,8 @@ void infer_multi(anh_runtime* h, const uint8_t* image, int H, int W, const doubl
         }
     });
     // the table's host vectors must outlive the async uploads: every replica's stream passes the uploads before the collective returns control below
-    if (total > 0) h->coll->all_reduce_sum(packed, (size_t)K * total, streams);   // the ONE exchange step of the path
-    h->each_replica([&](size_t r) {
-        DeviceScope scope(h->device_of(r));
-        Engine& e = h->replica(r);
+    if (total > 0) h->reps.coll->all_reduce_sum(packed, (size_t)K * total, streams);   // the ONE exchange step of the path
+    h->reps.each([&](size_t r, Engine& e) {
         if (hi[r] == lo[r]) return;
         if (total > 0) {
             anh_runtime::Exchange& x = h->exchange[r];
@@ -764,7 +682,7 @@ void infer_multi(anh_runtime* h, const uint8_t* image, int H, int W, const doubl
                                                (size_t)(rt - l + 1) * 4, (size_t)(b - t + 1), hipMemcpyDeviceToHost, e.stream));
         }
     });
-    for (size_t r = 0; r < R; ++r) { DeviceScope scope(h->device_of(r)); h->replica(r).synchronize(); }
+    h->reps.for_all([](size_t, Engine& e) { e.synchronize(); });
 }
 }  // namespace
 
@@ -773,33 +691,23 @@ int anh_infer(anh_runtime* h, const uint8_t* image, int height, int width, const
     return guarded([&] {
         ANH_REQUIRE(h && image && result, "null argument");
         ANH_REQUIRE(height >= 1 && width >= 1, "empty image");
-        DeviceScope scope(h->device_of(0));
-        Engine& e = *h->eng;
+        DeviceScope scope(h->reps.device_of(0));
+        Engine& e = h->reps.engine(0);
         const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
         const size_t plane = (size_t)height * width;
         std::vector<anh_tile> tiles = tiles_for(tiling, width, height);
         e.stage_image.reserve(plane * C);
         e.stage_blended.reserve(plane * K * 4);
         e.stage_result.reserve(plane * 2);
-        bool use_det = false;
-        if (detection_levels) for (int k = 0; k < K; ++k) { ANH_REQUIRE(detection_levels[k] >= 0.0, "detection levels must be >= 0"); if (detection_levels[k] > 0.0) use_det = true; }
+        const bool use_det = detection_requested(detection_levels, K);
         // several replicas: shard the tile list (the detection-level filter walks connected blobs of the WHOLE label map: it runs on
         // replica 0 alone, as does an image with fewer tiles than replicas would gain nothing)
-        if (h->replicas() > 1 && !use_det && tiles.size() >= 2) { infer_multi(h, image, height, width, gains, tiles, result, blended_out); return; }
-        static const bool streamed = !(getenv("ANH_INFER_STREAMED") && atoi(getenv("ANH_INFER_STREAMED")) == 0);
+        if (h->reps.size() > 1 && !use_det && tiles.size() >= 2) { infer_multi(h, image, height, width, gains, tiles, result, blended_out); return; }
+        static const bool streamed = read_switch("ANH_INFER_STREAMED", true);
         if (streamed && !use_det && !blended_out) { infer_streamed(h, image, height, width, gains, tiles, result); return; }
         HIP_CHECK(hipMemcpyAsync(e.stage_image.p, image, plane * C, hipMemcpyHostToDevice, e.stream));
         e.infer_device(e.stage_image.as<uint8_t>(), height, width, gains, tiles, e.stage_result.as<uint16_t>(), e.stage_blended.as<float>(), /*whole_image=*/true);
-        if (use_det) {
-            // detection-level filter (annonet_infer.cpp:187-239), on the resident planes and label map.  Seeds are looked up at
-            // (row, col): the reference stores (r, c) but reads (point.y(), point.x()) — transposed (:210 vs :222); see DESIGN.md.
-            e.stage_out.reserve(plane + (size_t)K * sizeof(double) + 64);
-            uint8_t* flags = e.stage_out.as<uint8_t>();
-            double* d_det = reinterpret_cast<double*>(flags + ((plane + 15) / 16) * 16);
-            int* d_changed = reinterpret_cast<int*>(d_det + K);
-            HIP_CHECK(hipMemcpyAsync(d_det, detection_levels, (size_t)K * sizeof(double), hipMemcpyHostToDevice, e.stream));
-            run_detection_filter(e.stage_blended.as<float>(), e.stage_result.as<uint16_t>(), K, height, width, d_det, flags, d_changed, e.stream);
-        }
+        if (use_det) apply_detection_levels(e, detection_levels, K, height, width);
         HIP_CHECK(hipMemcpyAsync(result, e.stage_result.p, plane * 2, hipMemcpyDeviceToHost, e.stream));
         if (blended_out) HIP_CHECK(hipMemcpyAsync(blended_out, e.stage_blended.p, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
         e.synchronize();
@@ -850,8 +758,8 @@ int anh_infer_scaled_device(anh_runtime* h, const uint8_t* d_image, int height, 
         ANH_REQUIRE(h && d_image && d_result, "null argument");
         int sh = 0, sw = 0;
         scaled_dims_checked(height, width, downscaling_factor, sh, sw);
-        DeviceScope scope(h->device_of(0));
-        Engine& e = *h->eng;
+        DeviceScope scope(h->reps.device_of(0));
+        Engine& e = h->reps.engine(0);
         const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
         const size_t plane = (size_t)sh * sw;
         const std::vector<anh_tile> tiles = tiles_for(tiling, sw, sh);
@@ -882,18 +790,17 @@ int anh_infer_scaled(anh_runtime* h, const uint8_t* image, int height, int width
             if (scaled_labels) std::memcpy(scaled_labels, result, full * 2);
             return;
         }
-        DeviceScope scope(h->device_of(0));
-        Engine& e = *h->eng;
+        DeviceScope scope(h->reps.device_of(0));
+        Engine& e = h->reps.engine(0);
         const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
         const std::vector<anh_tile> tiles = tiles_for(tiling, sw, sh);
-        bool use_det = false;
-        if (detection_levels) for (int k = 0; k < K; ++k) { ANH_REQUIRE(detection_levels[k] >= 0.0, "detection levels must be >= 0"); if (detection_levels[k] > 0.0) use_det = true; }
+        const bool use_det = detection_requested(detection_levels, K);
         e.stage_original.reserve(full * C);
         e.stage_image.reserve(plane * C);
         e.stage_blended.reserve(plane * K * 4);
         e.stage_result.reserve(plane * 2);
         e.stage_upsampled.reserve(full * 2);
-        if (h->replicas() > 1 && !use_det && tiles.size() >= 2) {
+        if (h->reps.size() > 1 && !use_det && tiles.size() >= 2) {
             // the sharded path (infer_multi): every replica shrinks the image itself; the merged map is assembled on the host from the
             // owners of its tiles, as for anh_infer, and replica 0 blows it up
             std::vector<uint16_t> merged_own;
@@ -911,14 +818,7 @@ int anh_infer_scaled(anh_runtime* h, const uint8_t* image, int height, int width
         HIP_CHECK(hipMemcpyAsync(e.stage_original.p, image, full * C, hipMemcpyHostToDevice, e.stream));
         e.resize_image(e.stage_original.as<uint8_t>(), height, width, e.stage_image.as<uint8_t>(), sh, sw);
         e.infer_device(e.stage_image.as<uint8_t>(), sh, sw, gains, tiles, e.stage_result.as<uint16_t>(), e.stage_blended.as<float>(), /*whole_image=*/true);
-        if (use_det) {
-            e.stage_out.reserve(plane + (size_t)K * sizeof(double) + 64);
-            uint8_t* flags = e.stage_out.as<uint8_t>();
-            double* d_det = reinterpret_cast<double*>(flags + ((plane + 15) / 16) * 16);
-            int* d_changed = reinterpret_cast<int*>(d_det + K);
-            HIP_CHECK(hipMemcpyAsync(d_det, detection_levels, (size_t)K * sizeof(double), hipMemcpyHostToDevice, e.stream));
-            run_detection_filter(e.stage_blended.as<float>(), e.stage_result.as<uint16_t>(), K, sh, sw, d_det, flags, d_changed, e.stream);
-        }
+        if (use_det) apply_detection_levels(e, detection_levels, K, sh, sw);
         e.resize_labels(e.stage_result.as<uint16_t>(), sh, sw, e.stage_upsampled.as<uint16_t>(), height, width);
         HIP_CHECK(hipMemcpyAsync(result, e.stage_upsampled.p, full * 2, hipMemcpyDeviceToHost, e.stream));
         if (scaled_labels) HIP_CHECK(hipMemcpyAsync(scaled_labels, e.stage_result.p, plane * 2, hipMemcpyDeviceToHost, e.stream));
@@ -927,16 +827,23 @@ int anh_infer_scaled(anh_runtime* h, const uint8_t* image, int height, int width
     });
 }
 
-int anh_runtime_set_stream(anh_runtime* h, void* s) { return guarded([&] { ANH_REQUIRE(h, "null handle"); ANH_REQUIRE(h->replicas() == 1, "a handle that drives several devices keeps its own streams"); h->eng->set_stream((hipStream_t)s); }); }
-int anh_runtime_get_stream(anh_runtime* h, void** s) { return guarded([&] { ANH_REQUIRE(h && s, "null argument"); *s = (void*)h->eng->stream; }); }
-int anh_runtime_stores_activations(anh_runtime* h, int* yes) { return guarded([&] { ANH_REQUIRE(h && yes, "null argument"); *yes = h->eng->infer_post ? 1 : 0; }); }
+int anh_runtime_set_stream(anh_runtime* h, void* s) { return guarded([&] { ANH_REQUIRE(h, "null handle"); ANH_REQUIRE(h->reps.size() == 1, "a handle that drives several devices keeps its own streams"); h->reps.engine(0).set_stream((hipStream_t)s); }); }
+int anh_runtime_get_stream(anh_runtime* h, void** s) { return guarded([&] { ANH_REQUIRE(h && s, "null argument"); *s = (void*)h->reps.engine(0).stream; }); }
+int anh_runtime_stores_activations(anh_runtime* h, int* yes) { return guarded([&] { ANH_REQUIRE(h && yes, "null argument"); *yes = h->reps.engine(0).infer_post ? 1 : 0; }); }
 int anh_runtime_synchronize(anh_runtime* h) {
-    return guarded([&] { ANH_REQUIRE(h, "null handle"); for (size_t r = 0; r < h->replicas(); ++r) { DeviceScope scope(h->device_of(r)); h->replica(r).synchronize(); } });
+    return guarded([&] { ANH_REQUIRE(h, "null handle"); h->reps.for_all([](size_t, Engine& e) { e.synchronize(); }); });
 }
 
 // ---- TrainingNet ----
 int anh_trainer_create(anh_trainer** out) {
-    return guarded([&] { ANH_REQUIRE(out, "null argument"); auto h = std::make_unique<anh_trainer>(); h->devices = selected_devices(); *out = h.release(); });
+    return guarded([&] {
+        ANH_REQUIRE(out, "null argument");
+        auto h = std::make_unique<anh_trainer>();
+        h->reps.devices = selected_devices();
+        h->stage = std::vector<std::array<anh_trainer::StageSet, 2>>(h->reps.size());
+        h->copy_stream = std::vector<Stream>(h->reps.size());
+        *out = h.release();
+    });
 }
 void anh_trainer_destroy(anh_trainer* h) { delete h; }
 
@@ -965,11 +872,11 @@ int anh_trainer_initialize(anh_trainer* h) {
         (void)Spec::build(h->cfg);  // validates the configuration
         h->initialized = true;
         h->dirty = true;
-        if (!h->loss_ring) {
+        if (!h->loss_ring.p) {
             // portable + mapped: the update kernel of replica 0 writes it, whichever device that replica lives on (anh_set_devices may come later)
-            HIP_CHECK(hipHostMalloc((void**)&h->loss_ring, 256 * sizeof(unsigned long long), hipHostMallocPortable | hipHostMallocMapped));
-            std::memset(h->loss_ring, 0, 256 * sizeof(unsigned long long));
-            HIP_CHECK(hipHostGetDevicePointer((void**)&h->loss_ring_dev, h->loss_ring, 0));
+            h->loss_ring.reserve(256 * sizeof(unsigned long long), hipHostMallocPortable | hipHostMallocMapped);
+            std::memset(h->loss_ring.p, 0, h->loss_ring.bytes);
+            HIP_CHECK(hipHostGetDevicePointer((void**)&h->loss_ring_dev, h->loss_ring.p, 0));
         }
     });
 }
@@ -1011,14 +918,11 @@ int anh_trainer_forward_backward_device(anh_trainer* h, const uint8_t* d_images,
     return guarded([&] {
         ANH_REQUIRE(h && d_images && d_labels && d_weights, "null argument");
         ANH_REQUIRE(loss_scale_n > 0, "loss scale batch must be positive");
-        ANH_REQUIRE(h->replicas() == 1, "device-resident steps drive ONE device: a handle over several devices takes host mini-batches (anh_trainer_step)");
-        DeviceScope scope(h->device_of(0));
+        ANH_REQUIRE(h->reps.size() == 1, "device-resident steps drive ONE device: a handle over several devices takes host mini-batches (anh_trainer_step)");
+        DeviceScope scope(h->reps.device_of(0));
         Engine& e = h->engine();
-        Src img;
-        img.kind = SRC_IMAGE; img.img = d_images; img.img_h = height; img.img_w = width;
-        img.img_sample_stride = (int64_t)height * width * e.spec.cfg.in_channels;
         e.bn_window = h->bn_window;
-        e.forward_training(img, n, height, width);
+        e.forward_training(image_source(d_images, height, width, e.spec.cfg.in_channels), n, height, width);
         e.backward(d_labels, d_weights, loss_scale_n);
     });
 }
@@ -1029,8 +933,8 @@ int anh_trainer_apply_update(anh_trainer* h, double grad_scale) {
         Engine& e = h->engine();
         // this is step h->steps + 1: its rate is decided by the losses of steps <= h->steps + 1 - kLossLag (deterministic lag)
         if (h->steps + 1 > anh_trainer::kLossLag) h->record_until(h->steps + 1 - anh_trainer::kLossLag);
-        for (size_t r = 1; r < h->replicas(); ++r) { DeviceScope scope(h->device_of(r)); h->replica(r).apply_update(h->sched.lr, h->weight_decay, h->momentum, grad_scale, h->bn_window); }
-        DeviceScope scope0(h->device_of(0));
+        for (size_t r = 1; r < h->reps.size(); ++r) { DeviceScope scope(h->reps.device_of(r)); h->reps.engine(r).apply_update(h->sched.lr, h->weight_decay, h->momentum, grad_scale, h->bn_window); }
+        DeviceScope scope0(h->reps.device_of(0));
         // the update kernel also ships this step's loss (gradient bucket's trailing slot: already all-reduced under data parallelism)
         const int slot = h->next_slot;
         h->next_slot = (h->next_slot + 1) % 256;
@@ -1059,35 +963,29 @@ namespace {
 // Packs samples of a host mini-batch into one of a replica's two pinned staging sets, uploads them on the replica's copy stream
 // and enqueues forward + backward behind the upload.  Returns once the inputs are packed (the host refills its vectors right
 // after StartTraining returns, annonet_train_main.cpp:585-586); packing step k+1 overlaps the GPU work of step k.
-anh_trainer::StageSet& stage_and_run(anh_trainer* h, Engine& e, anh_trainer::StageSet* sets, hipStream_t& copy_stream, const uint8_t* const* images,
-                                     const anh_wlabel* const* labels, int n, int height, int width, double loss_scale_n) {
+anh_trainer::StageSet& stage_and_run(anh_trainer* h, size_t r, Engine& e, const uint8_t* const* images, const anh_wlabel* const* labels, int n, int height,
+                                     int width, double loss_scale_n) {
     const int C = e.spec.cfg.in_channels, K = e.spec.cfg.classes;
     const size_t plane = (size_t)height * width;
-    const size_t img_bytes = (size_t)n * plane * C, lab_off = (img_bytes + 255) / 256 * 256, lab_bytes = (size_t)n * plane * 2;
-    const size_t w_off = (lab_off + lab_bytes + 255) / 256 * 256, total = w_off + (size_t)n * plane * 4;
-    anh_trainer::StageSet& st = sets[h->host_steps & 1];
-    if (!copy_stream) HIP_CHECK(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
-    if (!st.uploaded) {
-        HIP_CHECK(hipEventCreateWithFlags(&st.uploaded, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&st.consumed, hipEventDisableTiming));
-    }
+    const BatchLayout lay((size_t)n, plane, C);
+    anh_trainer::StageSet& st = h->stage[r][h->host_steps & 1];
+    if (!h->copy_stream[r].get()) h->copy_stream[r].create(hipStreamNonBlocking);
+    const hipStream_t copy_stream = h->copy_stream[r].get();
+    const hipEvent_t uploaded = st.uploaded.ensure(), consumed = st.consumed.ensure();
     if (st.in_flight) {   // the pinned block is free again once the upload of step k-2 is done: the one place a call blocks on the GPU
         const auto w0 = std::chrono::steady_clock::now();
-        wait_event(st.uploaded, h->replicas() > 1);
+        wait_event(uploaded, h->reps.size() > 1);
         st.wait_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
     } else st.wait_us = 0;
-    if (total > st.pinned_bytes) {
-        if (st.in_flight) wait_event(st.consumed, h->replicas() > 1);
-        if (st.pinned) HIP_CHECK(hipHostFree(st.pinned));
-        st.pinned = nullptr; st.pinned_bytes = 0;
-        HIP_CHECK(hipHostMalloc(&st.pinned, total, hipHostMallocDefault));
-        st.pinned_bytes = total;
-        st.dev.reserve(total);
+    if (lay.total > st.pinned.bytes) {
+        if (st.in_flight) wait_event(consumed, h->reps.size() > 1);
+        st.pinned.reserve(lay.total);
+        st.dev.reserve(lay.total);
     }
     // ---- pack: images as they are, weighted labels split into a u16 and an f32 plane; labels validated on the way ----
-    uint8_t* base = static_cast<uint8_t*>(st.pinned);
-    uint16_t* plab = reinterpret_cast<uint16_t*>(base + lab_off);
-    float* pw = reinterpret_cast<float*>(base + w_off);
+    uint8_t* base = st.pinned.as<uint8_t>();
+    uint16_t* plab = lay.labels(base);
+    float* pw = lay.weights(base);
     bool bad_label = false;
     for (int i = 0; i < n; ++i) {
         std::memcpy(base + (size_t)i * plane * C, images[i], plane * C);
@@ -1104,17 +1002,14 @@ anh_trainer::StageSet& stage_and_run(anh_trainer* h, Engine& e, anh_trainer::Sta
     }
     ANH_REQUIRE(!bad_label, "label value exceeds the class count");
     // ---- upload behind the step that last read this device block, compute behind the upload ----
-    if (st.in_flight) HIP_CHECK(hipStreamWaitEvent(copy_stream, st.consumed, 0));
-    HIP_CHECK(hipMemcpyAsync(st.dev.p, st.pinned, total, hipMemcpyHostToDevice, copy_stream));
-    HIP_CHECK(hipEventRecord(st.uploaded, copy_stream));
-    HIP_CHECK(hipStreamWaitEvent(e.stream, st.uploaded, 0));
+    if (st.in_flight) HIP_CHECK(hipStreamWaitEvent(copy_stream, consumed, 0));
+    HIP_CHECK(hipMemcpyAsync(st.dev.p, st.pinned.p, lay.total, hipMemcpyHostToDevice, copy_stream));
+    HIP_CHECK(hipEventRecord(uploaded, copy_stream));
+    HIP_CHECK(hipStreamWaitEvent(e.stream, uploaded, 0));
     uint8_t* dbase = st.dev.as<uint8_t>();
-    Src img;
-    img.kind = SRC_IMAGE; img.img = dbase; img.img_h = height; img.img_w = width;
-    img.img_sample_stride = (int64_t)height * width * C;
     e.bn_window = h->bn_window;
-    e.forward_training(img, n, height, width);
-    e.backward(reinterpret_cast<uint16_t*>(dbase + lab_off), reinterpret_cast<float*>(dbase + w_off), loss_scale_n);
+    e.forward_training(image_source(dbase, height, width, C), n, height, width);
+    e.backward(lay.labels(dbase), lay.weights(dbase), loss_scale_n);
     return st;
 }
 }  // namespace
@@ -1126,32 +1021,31 @@ int anh_trainer_step(anh_trainer* h, const uint8_t* const* images, const anh_wla
         ANH_REQUIRE(n >= 1 && height >= 1 && width >= 1, "empty mini-batch");
         for (int i = 0; i < n; ++i) ANH_REQUIRE(images[i] && labels[i], "null sample");
         (void)h->engine();   // builds every replica on first use
-        const size_t R = h->replicas();
+        const size_t R = h->reps.size();
         ANH_REQUIRE((size_t)n >= R, "mini-batch smaller than the number of devices");
         // data parallel (annonet_train_main.cpp:583-614): replica r takes samples [n r / R, n (r+1) / R); the loss
         // scale 1/(N nr nc) uses the WHOLE batch, so the exchange step is a plain sum of the gradient buckets
         std::vector<anh_trainer::StageSet*> used(R, nullptr);
         const auto host_t0 = std::chrono::steady_clock::now();
-        h->each_replica([&](size_t r) {   // packing, upload and the step's launches of every replica in parallel (persistent worker threads)
-            DeviceScope scope(h->device_of(r));
+        h->reps.each([&](size_t r, Engine& e) {   // packing, upload and the step's launches of every replica in parallel (persistent worker threads)
             int64_t lo, hi;
             shard_range(n, (int)R, (int)r, lo, hi);
-            used[r] = &stage_and_run(h, h->replica(r), h->stage_of(r), h->copy_stream_of(r), images + lo, labels + lo, (int)(hi - lo), height, width, (double)n);
+            used[r] = &stage_and_run(h, r, e, images + lo, labels + lo, (int)(hi - lo), height, width, (double)n);
         });
         if (R > 1) {
             std::vector<float*> buckets(R);
             std::vector<hipStream_t> streams(R);
-            for (size_t r = 0; r < R; ++r) { buckets[r] = h->replica(r).grad_bucket(); streams[r] = h->replica(r).stream; }
-            const int64_t count = (int64_t)h->eng->spec.n_params + 1, first = h->eng->early_grad_first();   // the trailing slot carries the loss
-            static const bool early_on = !(getenv("ANH_EARLY_REDUCE") && atoi(getenv("ANH_EARLY_REDUCE")) == 0);
+            for (size_t r = 0; r < R; ++r) { buckets[r] = h->reps.engine(r).grad_bucket(); streams[r] = h->reps.engine(r).stream; }
+            const int64_t count = (int64_t)h->reps.engine(0).spec.n_params + 1, first = h->reps.engine(0).early_grad_first();   // the trailing slot carries the loss
+            static const bool early_on = read_switch("ANH_EARLY_REDUCE", true);
             static const int xs_every = getenv("ANH_EXCHANGE_SAMPLE") ? atoi(getenv("ANH_EXCHANGE_SAMPLE")) : 8;
             anh_trainer::ExchangeStats& xs = h->xs;
             const bool split = early_on && first > 0 && first < count - 1;
             bool sample = false;
             if (xs_every > 0 && h->host_steps % (unsigned long)xs_every == (unsigned long)xs_every - 1) {
                 h->collect_exchange_sample();   // (the previous sampled step ended long ago)
-                DeviceScope scope(h->device_of(0));
-                if (!xs.head0) for (hipEvent_t* ev : {&xs.tail0, &xs.tail1, &xs.head0, &xs.head1}) HIP_CHECK(hipEventCreate(ev));
+                DeviceScope scope(h->reps.device_of(0));
+                for (Event* ev : {&xs.tail0, &xs.tail1, &xs.head0, &xs.head1}) ev->ensure(hipEventDefault);
                 sample = true;
                 xs.split = split;
             }
@@ -1160,37 +1054,32 @@ int anh_trainer_step(anh_trainer* h, const uint8_t* const* images, const anh_wla
                 // (Engine::ev_early_grads): reduce it on side streams now, the short head on the replicas' own streams afterwards
                 std::vector<float*> tails(R);
                 std::vector<hipStream_t> side(R);
-                for (size_t r = 0; r < R; ++r) {
-                    DeviceScope scope(h->device_of(r));
-                    Engine& e = h->replica(r);
+                h->reps.for_all([&](size_t r, Engine& e) {
                     side[r] = e.early_reduce_stream();
-                    HIP_CHECK(hipStreamWaitEvent(side[r], e.ev_early_grads, 0));
+                    HIP_CHECK(hipStreamWaitEvent(side[r], e.ev_early_grads.get(), 0));
                     tails[r] = buckets[r] + first;
-                }
-                if (sample) { DeviceScope scope(h->device_of(0)); HIP_CHECK(hipEventRecord(xs.tail0, side[0])); }
-                h->coll->all_reduce_sum(tails, (size_t)(count - first), side);
-                if (sample) { DeviceScope scope(h->device_of(0)); HIP_CHECK(hipEventRecord(xs.tail1, side[0])); HIP_CHECK(hipEventRecord(xs.head0, streams[0])); }
-                h->coll->all_reduce_sum(buckets, (size_t)first, streams);
-                if (sample) { DeviceScope scope(h->device_of(0)); HIP_CHECK(hipEventRecord(xs.head1, streams[0])); xs.pending = true; }
-                for (size_t r = 0; r < R; ++r) {   // the update reads the whole bucket
-                    DeviceScope scope(h->device_of(r));
-                    Engine& e = h->replica(r);
-                    HIP_CHECK(hipEventRecord(e.ev_early_reduced, side[r]));
-                    HIP_CHECK(hipStreamWaitEvent(e.stream, e.ev_early_reduced, 0));
-                }
+                });
+                if (sample) { DeviceScope scope(h->reps.device_of(0)); HIP_CHECK(hipEventRecord(xs.tail0.get(), side[0])); }
+                h->reps.coll->all_reduce_sum(tails, (size_t)(count - first), side);
+                if (sample) { DeviceScope scope(h->reps.device_of(0)); HIP_CHECK(hipEventRecord(xs.tail1.get(), side[0])); HIP_CHECK(hipEventRecord(xs.head0.get(), streams[0])); }
+                h->reps.coll->all_reduce_sum(buckets, (size_t)first, streams);
+                if (sample) { DeviceScope scope(h->reps.device_of(0)); HIP_CHECK(hipEventRecord(xs.head1.get(), streams[0])); xs.pending = true; }
+                h->reps.for_all([&](size_t r, Engine& e) {   // the update reads the whole bucket
+                    HIP_CHECK(hipEventRecord(e.ev_early_reduced.get(), side[r]));
+                    HIP_CHECK(hipStreamWaitEvent(e.stream, e.ev_early_reduced.get(), 0));
+                });
             } else {
-                if (sample) { DeviceScope scope(h->device_of(0)); HIP_CHECK(hipEventRecord(xs.head0, streams[0])); }
-                h->coll->all_reduce_sum(buckets, (size_t)count, streams);
-                if (sample) { DeviceScope scope(h->device_of(0)); HIP_CHECK(hipEventRecord(xs.head1, streams[0])); xs.pending = true; }
+                if (sample) { DeviceScope scope(h->reps.device_of(0)); HIP_CHECK(hipEventRecord(xs.head0.get(), streams[0])); }
+                h->reps.coll->all_reduce_sum(buckets, (size_t)count, streams);
+                if (sample) { DeviceScope scope(h->reps.device_of(0)); HIP_CHECK(hipEventRecord(xs.head1.get(), streams[0])); xs.pending = true; }
             }
         }
         const int rc = anh_trainer_apply_update(h, 1.0);
         if (rc != ANH_OK) fail(rc, g_error);
-        for (size_t r = 0; r < R; ++r) {
-            DeviceScope scope(h->device_of(r));
-            HIP_CHECK(hipEventRecord(used[r]->consumed, h->replica(r).stream));
+        h->reps.for_all([&](size_t r, Engine& e) {
+            HIP_CHECK(hipEventRecord(used[r]->consumed.get(), e.stream));
             used[r]->in_flight = true;
-        }
+        });
         ++h->host_steps;
         h->xs.host_us_last = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - host_t0).count();
         h->xs.host_us_sum += h->xs.host_us_last;
@@ -1205,7 +1094,7 @@ int anh_trainer_exchange_stats(anh_trainer* h, anh_exchange_stats* out) {
         h->collect_exchange_sample();
         const anh_trainer::ExchangeStats& xs = h->xs;
         *out = anh_exchange_stats{};
-        out->replicas = (int)h->replicas();
+        out->replicas = (int)h->reps.size();
         out->steps = xs.calls;
         out->host_us_mean = xs.calls ? xs.host_us_sum / (double)xs.calls : 0.0;
         out->host_us_last = xs.host_us_last;
@@ -1216,10 +1105,10 @@ int anh_trainer_exchange_stats(anh_trainer* h, anh_exchange_stats* out) {
         out->allreduce_tail_us_last = xs.tail_us_last;
         out->allreduce_head_us_last = xs.head_us_last;
         out->early_reduce = xs.split ? 1 : 0;
-        out->uses_rccl = h->coll ? h->coll->transport() : 0;
+        out->uses_rccl = h->reps.coll ? h->reps.coll->transport() : 0;
         out->rccl_version = Collective::rccl_version();
-        out->worker_calls = h->workers ? (int64_t)(h->workers->calls() - xs.worker_calls_base) : 0;
-        out->bucket_bytes = h->eng ? ((int64_t)h->eng->spec.n_params + 1) * 4 : 0;
+        out->worker_calls = h->reps.workers ? (int64_t)(h->reps.workers->calls() - xs.worker_calls_base) : 0;
+        out->bucket_bytes = h->reps.built() ? ((int64_t)h->reps.engine(0).spec.n_params + 1) * 4 : 0;
     });
 }
 void anh_trainer_reset_exchange_stats(anh_trainer* h) {
@@ -1227,7 +1116,7 @@ void anh_trainer_reset_exchange_stats(anh_trainer* h) {
     try { h->collect_exchange_sample(); } catch (...) {}
     anh_trainer::ExchangeStats& xs = h->xs;
     xs.calls = 0; xs.host_us_sum = 0; xs.wait_us_sum = 0; xs.samples = 0; xs.tail_us_sum = 0; xs.head_us_sum = 0;
-    xs.worker_calls_base = h->workers ? h->workers->calls() : 0;
+    xs.worker_calls_base = h->reps.workers ? h->reps.workers->calls() : 0;
 }
 
 int anh_trainer_grad_buffer(anh_trainer* h, void** d_ptr, int64_t* count) {
@@ -1246,17 +1135,17 @@ int anh_trainer_set_params(anh_trainer* h, const float* params, int64_t n_params
         ANH_REQUIRE(h && params && running, "null argument");
         Engine& e = h->engine();
         ANH_REQUIRE(n_params == e.spec.n_params && n_running == e.spec.n_running, "parameter blob size mismatch");
-        for (size_t r = 0; r < h->replicas(); ++r) { DeviceScope scope(h->device_of(r)); h->replica(r).synchronize(); h->replica(r).set_params(params, running); }
+        h->reps.for_all([&](size_t, Engine& er) { er.synchronize(); er.set_params(params, running); });
     });
 }
 int anh_trainer_replica_params(anh_trainer* h, int replica, float* params, int64_t n_params) {
     return guarded([&] {
         ANH_REQUIRE(h && params, "null argument");
         (void)h->engine();
-        ANH_REQUIRE(replica >= 0 && (size_t)replica < h->replicas(), "replica index out of range");
-        ANH_REQUIRE(n_params == h->eng->spec.n_params, "size mismatch");
-        DeviceScope scope(h->device_of((size_t)replica));
-        h->replica((size_t)replica).get_params(params, nullptr);
+        ANH_REQUIRE(replica >= 0 && (size_t)replica < h->reps.size(), "replica index out of range");
+        ANH_REQUIRE(n_params == h->reps.engine(0).spec.n_params, "size mismatch");
+        DeviceScope scope(h->reps.device_of((size_t)replica));
+        h->reps.engine((size_t)replica).get_params(params, nullptr);
     });
 }
 int anh_trainer_get_grads(anh_trainer* h, float* grads, int64_t n_params) {
@@ -1269,7 +1158,7 @@ int anh_trainer_set_momentum(anh_trainer* h, const float* m, int64_t n_params) {
     return guarded([&] {
         ANH_REQUIRE(h && m, "null argument");
         ANH_REQUIRE(n_params == h->engine().spec.n_params, "size mismatch");
-        for (size_t r = 0; r < h->replicas(); ++r) { DeviceScope scope(h->device_of(r)); h->replica(r).set_momentum(m); }
+        h->reps.for_all([&](size_t, Engine& e) { e.set_momentum(m); });
     });
 }
 
@@ -1286,7 +1175,7 @@ int anh_trainer_snapshot_runtime(anh_trainer* h, int precision, anh_runtime** ou
         // engines, no second ncclCommInitAll.  Handles the caller creates for inference (anh_runtime_create / _deserialize) span the
         // selected devices.
         auto rt = std::make_unique<anh_runtime>();
-        rt->build(cfg, h->replicas() > 1 ? h->device_of(0) : -1);
+        rt->build(cfg, h->reps.size() > 1 ? h->reps.device_of(0) : -1);
         rt->set_params_all(p.data(), r.data());
         *out = rt.release();
     });
@@ -1356,21 +1245,19 @@ void load_state_into(anh_trainer* h, Engine& e, const char* path) {
     std::vector<float> p((size_t)s.n_params), m((size_t)s.n_params), r((size_t)s.n_running);
     f.read((char*)p.data(), p.size() * 4); f.read((char*)m.data(), m.size() * 4); f.read((char*)r.data(), r.size() * 4);
     if (!f) fail(ANH_ERR_IO, "trainer state file is truncated");
-    for (size_t rr = 0; rr < h->replicas(); ++rr) {   // every replica resumes from the same state
-        DeviceScope scope(h->device_of(rr));
-        Engine& er = h->replica(rr);
+    h->reps.for_all([&](size_t, Engine& er) {   // every replica resumes from the same state
         er.synchronize();
         er.set_params(p.data(), r.data());
         er.set_momentum(m.data());
         er.set_running_updates(updates);
-    }
+    });
     h->pending = unrec;
     h->steps = (unsigned long)steps; h->last_loss = last_loss;
     h->sched.lr = lr; h->sched.check_budget = (unsigned long)budget; h->sched.steps_without_progress = (unsigned long)swp; h->sched.history = hist;
 }
 }  // namespace
 
-void anh_trainer::resume() { load_state_into(this, *eng, sync_path.c_str()); }
+void anh_trainer::resume() { load_state_into(this, reps.engine(0), sync_path.c_str()); }
 
 int anh_trainer_load_state(anh_trainer* h, const char* path) {
     return guarded([&] {
@@ -1381,14 +1268,14 @@ int anh_trainer_load_state(anh_trainer* h, const char* path) {
 }
 
 int anh_trainer_set_stream(anh_trainer* h, void* s) {
-    return guarded([&] { ANH_REQUIRE(h, "null handle"); ANH_REQUIRE(h->replicas() == 1, "a handle that drives several devices keeps its own streams"); h->engine().set_stream((hipStream_t)s); });
+    return guarded([&] { ANH_REQUIRE(h, "null handle"); ANH_REQUIRE(h->reps.size() == 1, "a handle that drives several devices keeps its own streams"); h->engine().set_stream((hipStream_t)s); });
 }
 int anh_trainer_get_stream(anh_trainer* h, void** s) { return guarded([&] { ANH_REQUIRE(h && s, "null argument"); *s = (void*)h->engine().stream; }); }
 int anh_trainer_early_grads(anh_trainer* h, int64_t* first) {
     return guarded([&] {
         ANH_REQUIRE(h && first, "null argument");
         Engine& e = h->engine();
-        *first = h->replicas() > 1 ? (int64_t)e.spec.n_params + 1 : e.early_grad_first();   // (several replicas: the library reduces the buckets itself)
+        *first = h->reps.size() > 1 ? (int64_t)e.spec.n_params + 1 : e.early_grad_first();   // (several replicas: the library reduces the buckets itself)
     });
 }
 int anh_trainer_step_graph_stats(anh_trainer* h, int64_t* captures, int64_t* launches) {
@@ -1403,7 +1290,7 @@ int anh_trainer_wait_early_grads(anh_trainer* h, void* hip_stream) {
         ANH_REQUIRE(h && hip_stream, "null argument");
         Engine& e = h->engine();
         ANH_REQUIRE(e.early_grad_first() <= e.spec.n_params, "this net has no early gradient part");
-        HIP_CHECK(hipStreamWaitEvent((hipStream_t)hip_stream, e.ev_early_grads, 0));
+        HIP_CHECK(hipStreamWaitEvent((hipStream_t)hip_stream, e.ev_early_grads.get(), 0));
     });
 }
 int anh_trainer_synchronize(anh_trainer* h) {
@@ -1411,11 +1298,10 @@ int anh_trainer_synchronize(anh_trainer* h) {
         ANH_REQUIRE(h, "null handle");
         (void)h->engine();
         bool bad = false;
-        for (size_t r = 0; r < h->replicas(); ++r) {
-            DeviceScope scope(h->device_of(r));
-            h->replica(r).synchronize();
-            bad = h->replica(r).read_error_flag_and_clear() || bad;
-        }
+        h->reps.for_all([&](size_t, Engine& e) {
+            e.synchronize();
+            bad = e.read_error_flag_and_clear() || bad;
+        });
         if (bad) fail(ANH_ERR_INVALID, "a label value exceeds the class count");
     });
 }
@@ -1426,7 +1312,7 @@ int anh_trainer_layer_tensor(anh_trainer* h, int layer, int which, float* out, i
 // ---- profiling ----
 static Engine* engine_of(void* handle, int is_trainer) {
     ANH_REQUIRE(handle, "null handle");
-    return is_trainer ? &((anh_trainer*)handle)->engine() : ((anh_runtime*)handle)->eng.get();
+    return is_trainer ? &((anh_trainer*)handle)->engine() : &((anh_runtime*)handle)->reps.engine(0);
 }
 int anh_profile_enable(void* handle, int is_trainer, int enable) {
     return guarded([&] { Engine* e = engine_of(handle, is_trainer); e->synchronize(); e->prof.enabled = enable != 0; });
@@ -1495,7 +1381,7 @@ int anh_dataset_create(int channels, anh_dataset** out) {
         if (hipGetDeviceCount(&count) != hipSuccess || count == 0) { (void)hipGetLastError(); fail(ANH_ERR_DEVICE, "no MI355X / HIP device visible"); }
         auto d = std::make_unique<anh_dataset>();
         d->channels = channels;
-        HIP_CHECK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+        d->stream.create(hipStreamNonBlocking);
         *out = d.release();
     });
 }
@@ -1521,7 +1407,7 @@ int anh_dataset_remove(anh_dataset* d, int index) {
     return guarded([&] {
         ANH_REQUIRE(d, "null dataset");
         ANH_REQUIRE(index >= 0 && (size_t)index < d->items.size() && d->items[(size_t)index].height > 0, "dataset remove: no such image");
-        HIP_CHECK(hipStreamSynchronize(d->stream));   // the crop kernels that read the image have finished
+        HIP_CHECK(hipStreamSynchronize(d->stream.get()));   // the crop kernels that read the image have finished
         anh_dataset::Item& it = d->items[(size_t)index];
         d->resident_bytes -= (uint64_t)it.height * it.width * (d->channels + 2);
         it.image.release(); it.labels.release(); it.height = it.width = 0;
@@ -1535,17 +1421,18 @@ int anh_dataset_crop_batch(anh_dataset* d, const anh_crop_spec* specs, int n, in
                            uint8_t* images, anh_wlabel* labels) {
     return guarded([&] {
         ANH_REQUIRE(d && specs && images && labels && n >= 1 && dim >= 1, "crop batch: bad argument");
-        const size_t plane = (size_t)dim * dim, img = (size_t)n * plane * d->channels;
-        const size_t lab_off = (img + 255) / 256 * 256, w_off = (lab_off + (size_t)n * plane * 2 + 255) / 256 * 256;
-        d->out.reserve(w_off + (size_t)n * plane * 4);
+        const size_t plane = (size_t)dim * dim;
+        const BatchLayout lay((size_t)n, plane, d->channels);
+        const hipStream_t stream = d->stream.get();
+        d->out.reserve(lay.total);
         uint8_t* base = d->out.as<uint8_t>();
-        d->crop_batch(specs, n, dim, classes, class_weight, image_weight, base, reinterpret_cast<uint16_t*>(base + lab_off), reinterpret_cast<float*>(base + w_off));
+        d->crop_batch(specs, n, dim, classes, class_weight, image_weight, base, lay.labels(base), lay.weights(base));
         std::vector<uint16_t> hl((size_t)n * plane);
         std::vector<float> hw((size_t)n * plane);
-        HIP_CHECK(hipMemcpyAsync(images, base, img, hipMemcpyDeviceToHost, d->stream));
-        HIP_CHECK(hipMemcpyAsync(hl.data(), base + lab_off, hl.size() * 2, hipMemcpyDeviceToHost, d->stream));
-        HIP_CHECK(hipMemcpyAsync(hw.data(), base + w_off, hw.size() * 4, hipMemcpyDeviceToHost, d->stream));
-        HIP_CHECK(hipStreamSynchronize(d->stream));
+        HIP_CHECK(hipMemcpyAsync(images, base, lay.img_bytes, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(hl.data(), lay.labels(base), hl.size() * 2, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(hw.data(), lay.weights(base), hw.size() * 4, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
         for (size_t i = 0; i < hl.size(); ++i) { labels[i].label = hl[i]; labels[i].weight = hw[i]; }
     });
 }
@@ -1553,32 +1440,28 @@ int anh_trainer_step_crops(anh_trainer* h, anh_dataset* d, const anh_crop_spec* 
     return guarded([&] {
         ANH_REQUIRE(h && d && specs, "null argument");
         ANH_REQUIRE(n >= 1 && dim >= 1, "empty mini-batch");
-        ANH_REQUIRE(h->replicas() == 1, "device-cut crops live on ONE device: a handle over several devices takes host mini-batches (anh_trainer_step)");
+        ANH_REQUIRE(h->reps.size() == 1, "device-cut crops live on ONE device: a handle over several devices takes host mini-batches (anh_trainer_step)");
         Engine& e = h->engine();
         const int C = e.spec.cfg.in_channels, K = e.spec.cfg.classes;
         ANH_REQUIRE(C == d->channels, "the dataset's channel count differs from the net's");
-        const size_t plane = (size_t)dim * dim, img_bytes = (size_t)n * plane * C, lab_off = (img_bytes + 255) / 256 * 256;
-        const size_t w_off = (lab_off + (size_t)n * plane * 2 + 255) / 256 * 256, total = w_off + (size_t)n * plane * 4;
-        anh_trainer::StageSet& st = h->stage[h->host_steps & 1];
-        if (!st.uploaded) {
-            HIP_CHECK(hipEventCreateWithFlags(&st.uploaded, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&st.consumed, hipEventDisableTiming));
-        }
-        if (total > st.dev.bytes) {
-            if (st.in_flight) wait_event(st.consumed, h->replicas() > 1);
-            st.dev.reserve(total);
+        const BatchLayout lay((size_t)n, (size_t)dim * dim, C);
+        anh_trainer::StageSet& st = h->stage[0][h->host_steps & 1];
+        const hipEvent_t uploaded = st.uploaded.ensure(), consumed = st.consumed.ensure();
+        if (lay.total > st.dev.bytes) {
+            if (st.in_flight) wait_event(consumed, h->reps.size() > 1);
+            st.dev.reserve(lay.total);
         }
         // the crops of step k are cut on the dataset's stream while the trainer's stream still runs step k-1
-        if (st.in_flight) HIP_CHECK(hipStreamWaitEvent(d->stream, st.consumed, 0));
+        if (st.in_flight) HIP_CHECK(hipStreamWaitEvent(d->stream.get(), consumed, 0));
         uint8_t* dbase = st.dev.as<uint8_t>();
-        d->crop_batch(specs, n, dim, K, class_weight, image_weight, dbase, reinterpret_cast<uint16_t*>(dbase + lab_off), reinterpret_cast<float*>(dbase + w_off));
-        HIP_CHECK(hipEventRecord(st.uploaded, d->stream));
-        HIP_CHECK(hipStreamWaitEvent(e.stream, st.uploaded, 0));
-        int rc = anh_trainer_forward_backward_device(h, dbase, reinterpret_cast<uint16_t*>(dbase + lab_off), reinterpret_cast<float*>(dbase + w_off), n, dim, dim, (double)n);
+        d->crop_batch(specs, n, dim, K, class_weight, image_weight, dbase, lay.labels(dbase), lay.weights(dbase));
+        HIP_CHECK(hipEventRecord(uploaded, d->stream.get()));
+        HIP_CHECK(hipStreamWaitEvent(e.stream, uploaded, 0));
+        int rc = anh_trainer_forward_backward_device(h, dbase, lay.labels(dbase), lay.weights(dbase), n, dim, dim, (double)n);
         if (rc != ANH_OK) fail(rc, g_error);
         rc = anh_trainer_apply_update(h, 1.0);
         if (rc != ANH_OK) fail(rc, g_error);
-        HIP_CHECK(hipEventRecord(st.consumed, e.stream));
+        HIP_CHECK(hipEventRecord(consumed, e.stream));
         st.in_flight = true;
         ++h->host_steps;
     });

@@ -71,18 +71,17 @@ class Engine {
     DType dtype;
     bool training;
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = true;
+    hipStream_t stream = nullptr;   // the engine's own (own_stream_), or one borrowed through set_stream
     // filter gradients run on a second stream, concurrently with the backward-data / bn chain (both only read dy)
-    hipStream_t aux_stream = nullptr;
-    hipEvent_t ev_dy_ready = nullptr, ev_aux_done = nullptr;
+    Stream aux_stream;
+    Event ev_dy_ready, ev_aux_done;
     // Data-parallel hosts start the gradient all-reduce before backward has finished: the filter gradients come out last layer
     // first, so once layer kEarlyLayer's is reduced every gradient element from that layer's first parameter to the end of the
     // bucket (deeper layers, head, loss slot) is final.  ev_early_grads fires there (on the stream that ran that filter gradient).
     static constexpr int kEarlyLayer = 2;
-    hipEvent_t ev_early_grads = nullptr;
-    hipStream_t early_stream = nullptr;       // where the in-library exchange reduces the early part (anh_set_devices), made on first use
-    hipEvent_t ev_early_reduced = nullptr;
+    Event ev_early_grads;
+    Stream early_stream;       // where the in-library exchange reduces the early part (anh_set_devices), made on first use
+    Event ev_early_reduced;
     hipStream_t early_reduce_stream();
     int64_t early_grad_first() const;   // first bucket element covered by ev_early_grads; n_params + 1 when there is no early part
     bool concurrent_wgrad = true;
@@ -184,6 +183,7 @@ class Engine {
     Src last_image{};
     int last_n = 0, last_h = 0, last_w = 0;
     bool have_forward = false;
+    Stream own_stream_;   // owns `stream`; empty while a borrowed one is in use
 };
 
 }  // namespace anh

@@ -72,14 +72,13 @@ Engine::Engine(const anh_net_config& cfg, bool training_) : spec(Spec::build(cfg
     static const int prio = getenv("ANH_STREAM_PRIORITY") ? atoi(getenv("ANH_STREAM_PRIORITY")) : 0;
     int lo = 0, hi = 0;
     HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));   // lo = least urgent (numerically greatest)
-    if (prio && training) HIP_CHECK(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, hi));
-    else HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    if (prio && training) own_stream_.create_with_priority(hipStreamNonBlocking, hi);
+    else own_stream_.create(hipStreamNonBlocking);
+    stream = own_stream_.get();
     if (training) {
-        if (prio) HIP_CHECK(hipStreamCreateWithPriority(&aux_stream, hipStreamNonBlocking, prio == 2 ? hi : lo));
-        else HIP_CHECK(hipStreamCreateWithFlags(&aux_stream, hipStreamNonBlocking));
-        HIP_CHECK(hipEventCreateWithFlags(&ev_dy_ready, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&ev_aux_done, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&ev_early_grads, hipEventDisableTiming));
+        if (prio) aux_stream.create_with_priority(hipStreamNonBlocking, prio == 2 ? hi : lo);
+        else aux_stream.create(hipStreamNonBlocking);
+        ev_dy_ready.ensure(); ev_aux_done.ensure(); ev_early_grads.ensure();
         const char* e = getenv("ANH_CONCURRENT_WGRAD");
         if (e && e[0] == '0') concurrent_wgrad = false;
     }
@@ -130,31 +129,26 @@ Engine::Engine(const anh_net_config& cfg, bool training_) : spec(Spec::build(cfg
 }
 
 // Every stream the engine launched on is drained before anything it owns is destroyed, whatever the host still holds (a torch
-// ExternalStream over `stream`, events recorded there, pinned copies in flight): destruction never races work in flight.
+// ExternalStream over `stream`, events recorded there, pinned copies in flight): destruction never races work in flight.  The
+// streams, events and buffers themselves go with the members, after this body.
 Engine::~Engine() {
     if (stream) (void)hipStreamSynchronize(stream);
-    if (early_stream) (void)hipStreamSynchronize(early_stream);
-    if (aux_stream) { (void)hipStreamSynchronize(aux_stream); (void)hipStreamDestroy(aux_stream); }
+    if (early_stream.get()) (void)hipStreamSynchronize(early_stream.get());
+    if (aux_stream.get()) (void)hipStreamSynchronize(aux_stream.get());
     for (StepGraph& c : step_graphs) if (c.exec) (void)hipGraphExecDestroy(c.exec);
-    if (ev_dy_ready) (void)hipEventDestroy(ev_dy_ready);
-    if (ev_aux_done) (void)hipEventDestroy(ev_aux_done);
-    if (ev_early_grads) (void)hipEventDestroy(ev_early_grads);
-    if (ev_early_reduced) (void)hipEventDestroy(ev_early_reduced);
-    if (early_stream) (void)hipStreamDestroy(early_stream);
-    if (stream && own_stream) (void)hipStreamDestroy(stream);
 }
 
 void Engine::set_stream(hipStream_t s) {
     synchronize();
-    if (own_stream && stream) (void)hipStreamDestroy(stream);
-    if (s) { stream = s; own_stream = false; }
-    else { HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); own_stream = true; }
+    own_stream_.reset();
+    stream = s;
+    if (!s) { own_stream_.create(hipStreamNonBlocking); stream = own_stream_.get(); }
 }
 
 void Engine::synchronize() {
     const bool bounded = bounded_waits;
     wait_stream(stream, bounded);
-    if (aux_stream) wait_stream(aux_stream, bounded);
+    if (aux_stream.get()) wait_stream(aux_stream.get(), bounded);
     if (prof.enabled) prof.collect();
 }
 
@@ -275,7 +269,7 @@ void Engine::plan_dims(int n, int h, int w) {
     catch (const Error& e) {
         if (e.code == ANH_ERR_OOM) {
             (void)hipStreamSynchronize(stream);
-            if (aux_stream) (void)hipStreamSynchronize(aux_stream);
+            if (aux_stream.get()) (void)hipStreamSynchronize(aux_stream.get());
             for (LayerState& s : ls) { s.raw.release(); s.dact.release(); s.bwd_partials.release(); }
             logits.release(); dlogits.release(); loss_partials.release(); bn_partials.release();
             have_forward = false;
@@ -466,7 +460,7 @@ void Engine::wgrad_dispatch(WgradArgs& a, const char* tag, double flops, double 
     if (splits > 0) {  // fixed-order sum of the per-workgroup partials
         const int64_t nw = (int64_t)a.k * a.k * a.c_in * a.c_out;
         // (the reduce of a filter gradient that runs on the MAIN stream — the stem's, in the step's tail — has a name of its own: bench.py's critical_path)
-        tok = prof.begin(on, (on == stream && aux_stream && concurrent_wgrad) ? "wgrad_reduce_partials_main" : "wgrad_reduce_partials", 0, (double)splits * nw * 4.0);
+        tok = prof.begin(on, (on == stream && aux_stream.get() && concurrent_wgrad) ? "wgrad_reduce_partials_main" : "wgrad_reduce_partials", 0, (double)splits * nw * 4.0);
         launch_reduce_partials(a.partials, splits, nw, a.dw, on);
         prof.end(on, tok);
     }
@@ -551,11 +545,11 @@ bool Engine::head_is_fused() const {
 }
 
 hipStream_t Engine::early_reduce_stream() {
-    if (!early_stream) {
-        HIP_CHECK(hipStreamCreateWithFlags(&early_stream, hipStreamNonBlocking));
-        HIP_CHECK(hipEventCreateWithFlags(&ev_early_reduced, hipEventDisableTiming));
+    if (!early_stream.get()) {
+        early_stream.create(hipStreamNonBlocking);
+        ev_early_reduced.ensure();
     }
-    return early_stream;
+    return early_stream.get();
 }
 
 int64_t Engine::early_grad_first() const {
@@ -685,7 +679,7 @@ void Engine::backward(const uint16_t* d_labels, const float* d_weights, double l
         const void* dy;
         DType dy_dt;
         const double flops = 2.0 * L.k * L.k * L.cin * L.cout * (double)(L.type == 0 ? p_out : p_in);
-        const bool two_streams = concurrent_wgrad && aux_stream;
+        const bool two_streams = concurrent_wgrad && aux_stream.get();
 
         // backward-data conv of this layer (arguments first: whether it can take the bn backward in its prologue decides the schedule)
         ConvArgs dg;
@@ -775,9 +769,9 @@ void Engine::backward(const uint16_t* d_labels, const float* d_weights, double l
             static const bool tail_on_main = getenv("ANH_STEM_WGRAD_MAIN") ? atoi(getenv("ANH_STEM_WGRAD_MAIN")) != 0 : true;
             const bool on_main = two_streams && !has_dgrad && tail_on_main;
             if (two_streams && !on_main) {
-                HIP_CHECK(hipEventRecord(ev_dy_ready, stream));   // dy of this layer is final on the main stream: let the second stream pick it up
-                HIP_CHECK(hipStreamWaitEvent(aux_stream, ev_dy_ready, 0));
-                on = aux_stream;
+                HIP_CHECK(hipEventRecord(ev_dy_ready.get(), stream));   // dy of this layer is final on the main stream: let the second stream pick it up
+                HIP_CHECK(hipStreamWaitEvent(aux_stream.get(), ev_dy_ready.get(), 0));
+                on = aux_stream.get();
             }
             wgrad_dispatch(g, (std::string("wgrad_") + layer_tag(li, L)).c_str(), flops, bytes, on, on_main ? wgrad_partials_main : wgrad_partials);
         };
@@ -805,12 +799,12 @@ void Engine::backward(const uint16_t* d_labels, const float* d_weights, double l
         };
         run_wgrad();
         if (li == kEarlyLayer && early_grad_first() <= spec.n_params)   // gradients of layers >= kEarlyLayer, head and loss are final here
-            HIP_CHECK(hipEventRecord(ev_early_grads, (two_streams && has_dgrad) ? aux_stream : stream));
+            HIP_CHECK(hipEventRecord(ev_early_grads.get(), (two_streams && has_dgrad) ? aux_stream.get() : stream));
         if (has_dgrad) run_dgrad();
     }
-    if (concurrent_wgrad && aux_stream) {  // gradients are complete on the main stream only after the aux stream drains
-        HIP_CHECK(hipEventRecord(ev_aux_done, aux_stream));
-        HIP_CHECK(hipStreamWaitEvent(stream, ev_aux_done, 0));
+    if (concurrent_wgrad && aux_stream.get()) {  // gradients are complete on the main stream only after the aux stream drains
+        HIP_CHECK(hipEventRecord(ev_aux_done.get(), aux_stream.get()));
+        HIP_CHECK(hipStreamWaitEvent(stream, ev_aux_done.get(), 0));
     }
     };
     // ---- ANH_STEP_GRAPH=1 (round 5): the ~36 launches behind the head — both streams, the eight dy hand-overs and
@@ -825,7 +819,7 @@ void Engine::backward(const uint16_t* d_labels, const float* d_weights, double l
     mix((uint64_t)last_image.img_left); mix((uint64_t)last_image.img_top); mix((uint64_t)last_image.img_h); mix((uint64_t)last_image.img_w); mix((uint64_t)last_image.img_nwin);
     for (const LayerState& s : ls) { mix((uint64_t)(uintptr_t)s.raw.p); mix((uint64_t)(uintptr_t)s.dact.p); mix((uint64_t)(uintptr_t)s.bwd_partials.p); }
     mix((uint64_t)(uintptr_t)dlogits.p); mix((uint64_t)(uintptr_t)wgrad_partials.p); mix((uint64_t)(uintptr_t)wgrad_partials_main.p); mix((uint64_t)(uintptr_t)bn_partials.p);
-    mix((uint64_t)(uintptr_t)stream); mix((uint64_t)(uintptr_t)aux_stream); mix((uint64_t)tables); mix((uint64_t)concurrent_wgrad); mix((uint64_t)head_da_virtual); mix((uint64_t)head_bnred_blocks_);
+    mix((uint64_t)(uintptr_t)stream); mix((uint64_t)(uintptr_t)aux_stream.get()); mix((uint64_t)tables); mix((uint64_t)concurrent_wgrad); mix((uint64_t)head_da_virtual); mix((uint64_t)head_bnred_blocks_);
     StepGraph* g = nullptr;
     for (StepGraph& c : step_graphs) if (c.key == key) g = &c;
     if (!g) {

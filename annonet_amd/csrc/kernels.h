@@ -51,6 +51,13 @@ struct Src {
     __host__ __device__ int win_left(int n) const { return img_nwin ? img_win[2 * n] : img_left; }
     __host__ __device__ int win_top(int n) const { return img_nwin ? img_win[2 * n + 1] : img_top; }
 };
+// SRC_IMAGE over whole samples: [n][h][w][channels] u8 on the device, the window at the image's origin
+inline Src image_source(const uint8_t* d, int h, int w, int channels) {
+    Src s;
+    s.kind = SRC_IMAGE; s.img = d; s.img_h = h; s.img_w = w;
+    s.img_sample_stride = (int64_t)h * w * channels;
+    return s;
+}
 
 // out[n,oy,ox,co] = sum_{ky,kx,cr} src(n, iy, ix, cr) * w[(ky*k+kx)][cr][co]   (+ bias[co])
 //   gather = 0 ("con"):        iy = oy*stride + ky - pad

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "engine.h"
 
 namespace anh {
 
@@ -66,8 +67,8 @@ class Collective {
   private:
     std::vector<int> devices_;
     std::vector<void*> comms_;   // ncclComm_t
-    std::vector<hipEvent_t> ready_;
-    hipEvent_t done_ = nullptr;
+    std::vector<Event> ready_;
+    Event done_;
     DevBuf scratch_;
     bool peer_copies_ = false;
 };
@@ -90,7 +91,7 @@ void launch_unpack_rects(float* planes, int k, int height, int width, const anh_
 //
 // Round 4: the workers are PERSISTENT.  ReplicaWorkers lives with the handle (anh_trainer / anh_runtime): replicas - 1 threads, each
 // bound to one replica index, with its device selected once at thread start; a call is ONE wake-up (a generation counter under a
-// mutex + condition variable) and one wait for the stragglers.  Round 3's for_each_replica created and joined replicas - 1
+// mutex + condition variable) and one wait for the stragglers.  Round 3 created and joined replicas - 1
 // std::threads on every call — at eight replicas and a 1.6 ms step, seven thread creations per StartTraining, each new thread paying
 // its first hipSetDevice.  Every fn(r) touches only replica r's state; the first exception is rethrown on the caller.
 class ReplicaWorkers {
@@ -180,18 +181,41 @@ class ReplicaWorkers {
     bool stop_ = false;
 };
 
-// (the creating / joining form, kept for callers without a handle)
-template <class F>
-void for_each_replica(size_t replicas, F&& fn) {
-    if (replicas <= 1) { if (replicas == 1) fn((size_t)0); return; }
-    std::vector<std::exception_ptr> failed(replicas);
-    std::vector<std::thread> workers;
-    workers.reserve(replicas - 1);
-    for (size_t r = 1; r < replicas; ++r)
-        workers.emplace_back([&fn, &failed, r] { try { fn(r); } catch (...) { failed[r] = std::current_exception(); } });
-    try { fn((size_t)0); } catch (...) { failed[0] = std::current_exception(); }
-    for (std::thread& w : workers) w.join();
-    for (const std::exception_ptr& e : failed) if (e) std::rethrow_exception(e);
-}
+// The R replicas behind one handle (anh_runtime, anh_trainer): replica r is an Engine on devices[r].  What a handle keeps per
+// replica beyond the engine (staging sets, exchange scratch) stays with the handle, indexed by replica and declared BEFORE its
+// ReplicaSet, so that it outlives the engines.  Tear-down: the worker threads first (nothing of theirs outlives the replicas), then
+// the engines in reverse order, each drained and destroyed under its own device, then the collective.
+struct ReplicaSet {
+    std::vector<int> devices;   // empty = the creating thread's current device: one replica, and no hipSetDevice ever
+    std::unique_ptr<Collective> coll;
+    std::vector<std::unique_ptr<Engine>> engines;   // replica 0 included
+    std::unique_ptr<ReplicaWorkers> workers;        // persistent host threads, one per replica beyond the first
+    ReplicaSet() = default;
+    ~ReplicaSet() { workers.reset(); drop_engines(); }
+    ReplicaSet(const ReplicaSet&) = delete;
+    ReplicaSet& operator=(const ReplicaSet&) = delete;
+
+    size_t size() const { return devices.size() > 1 ? devices.size() : 1; }
+    int device_of(size_t r) const { return devices.empty() ? -1 : devices[r]; }
+    Engine& engine(size_t r) const { return *engines[r]; }
+    bool built() const { return !engines.empty(); }
+    // (Re)builds every replica; `seed` non-null: the SAME random_init on each, so that all start from the same weights.  The
+    // collective and the workers of a set that is built again are kept.
+    void build(std::vector<int> devs, const anh_net_config& cfg, bool training, const uint64_t* seed);
+    // fn(r, engine r) under replica r's device — in parallel, replica 0 on the calling thread and the others on their workers ...
+    template <class F>
+    void each(F&& fn) {
+        auto job = [&](size_t r) { DeviceScope scope(device_of(r)); fn(r, *engines[r]); };
+        if (workers) workers->run(job); else job((size_t)0);
+    }
+    // ... or one after the other on the calling thread
+    template <class F>
+    void for_all(F&& fn) {
+        for (size_t r = 0; r < engines.size(); ++r) { DeviceScope scope(device_of(r)); fn(r, *engines[r]); }
+    }
+
+  private:
+    void drop_engines();
+};
 
 }  // namespace anh

@@ -127,14 +127,10 @@ Collective::Collective(const std::vector<int>& devices) : devices_(devices) {
     }
     peer_copies_ = distinct && devices.size() > 1 && comms_.empty();
     if (comms_.empty()) {
-        for (size_t i = 0; i < devices.size(); ++i) {
-            DeviceScope scope(devices[i]);
-            hipEvent_t e;
-            HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ready_.push_back(e);
-        }
+        ready_ = std::vector<Event>(devices.size());
+        for (size_t i = 0; i < devices.size(); ++i) { DeviceScope scope(devices[i]); ready_[i].ensure(); }
         DeviceScope scope(devices[0]);
-        HIP_CHECK(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+        done_.ensure();
     }
 }
 
@@ -145,8 +141,6 @@ int Collective::rccl_version() {
 
 Collective::~Collective() {
     for (void* c : comms_) (void)ncclCommDestroy((ncclComm_t)c);
-    for (hipEvent_t e : ready_) (void)hipEventDestroy(e);
-    if (done_) (void)hipEventDestroy(done_);
 }
 
 void Collective::all_reduce_sum(const std::vector<float*>& bufs, size_t count, const std::vector<hipStream_t>& streams) {
@@ -165,12 +159,12 @@ void Collective::all_reduce_sum(const std::vector<float*>& bufs, size_t count, c
     // rehearsal backend: replica 0's stream waits for every producer, sums in replica order, hands the result back
     for (size_t i = 1; i < R; ++i) {
         DeviceScope scope(devices_[i]);
-        HIP_CHECK(hipEventRecord(ready_[i], streams[i]));
+        HIP_CHECK(hipEventRecord(ready_[i].get(), streams[i]));
     }
     DeviceScope scope(devices_[0]);
     const int blocks = (int)std::min<size_t>((count + 255) / 256, 256 * 8);
     for (size_t i = 1; i < R; ++i) {
-        HIP_CHECK(hipStreamWaitEvent(streams[0], ready_[i], 0));
+        HIP_CHECK(hipStreamWaitEvent(streams[0], ready_[i].get(), 0));
         const float* src = bufs[i];
         if (devices_[i] != devices_[0]) {
             scratch_.reserve(count * 4);
@@ -184,11 +178,31 @@ void Collective::all_reduce_sum(const std::vector<float*>& bufs, size_t count, c
         if (devices_[i] == devices_[0]) HIP_CHECK(hipMemcpyAsync(bufs[i], bufs[0], count * 4, hipMemcpyDeviceToDevice, streams[0]));
         else HIP_CHECK(hipMemcpyPeerAsync(bufs[i], devices_[i], bufs[0], devices_[0], count * 4, streams[0]));
     }
-    HIP_CHECK(hipEventRecord(done_, streams[0]));
+    HIP_CHECK(hipEventRecord(done_.get(), streams[0]));
     for (size_t i = 1; i < R; ++i) {
         DeviceScope s2(devices_[i]);
-        HIP_CHECK(hipStreamWaitEvent(streams[i], done_, 0));
+        HIP_CHECK(hipStreamWaitEvent(streams[i], done_.get(), 0));
     }
+}
+
+// ---------------------------------------------------------------------------------------------------
+void ReplicaSet::drop_engines() {
+    for (size_t r = engines.size(); r-- > 0;) { DeviceScope scope(device_of(r)); engines[r].reset(); }
+    engines.clear();
+}
+
+void ReplicaSet::build(std::vector<int> devs, const anh_net_config& cfg, bool training, const uint64_t* seed) {
+    drop_engines();
+    devices = std::move(devs);
+    engines.reserve(size());
+    for (size_t r = 0; r < size(); ++r) {
+        DeviceScope scope(device_of(r));
+        engines.push_back(std::make_unique<Engine>(cfg, training));
+        if (seed) engines.back()->random_init(*seed);
+        engines.back()->bounded_waits = size() > 1;   // host waits with a deadline (common.h)
+    }
+    if (size() > 1 && !coll) coll = std::make_unique<Collective>(devices);
+    if (size() > 1 && !workers) workers = std::make_unique<ReplicaWorkers>(devices);
 }
 
 }  // namespace anh

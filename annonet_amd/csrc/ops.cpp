@@ -44,10 +44,12 @@ inline float from_bf16_bits(uint16_t b) {
     return v;
 }
 
-struct Stream {
+// the stream of one entry point: synchronised before it is destroyed, also when an error unwinds past launched work
+struct OpStream {
+    Stream own;
     hipStream_t s = nullptr;
-    Stream() { HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-    ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    OpStream() { own.create(hipStreamNonBlocking); s = own.get(); }
+    ~OpStream() { (void)hipStreamSynchronize(s); }
 };
 
 // host fp32 -> device tensor in the mode's storage type
@@ -137,13 +139,6 @@ int out_dim(const anh_conv_desc& d, int in) {
     anh_layer_desc L{};
     L.type = d.type; L.k = d.k; L.stride = d.stride; L.pad = d.pad;
     return Spec::out_dim(L, in);
-}
-
-template <typename F>
-int guarded(F&& f) {
-    try { f(); return ANH_OK; }
-    catch (const Error& e) { set_last_error(e.what()); return e.code; }
-    catch (const std::exception& e) { set_last_error(e.what()); return ANH_ERR_INTERNAL; }
 }
 
 // ---- helpers of the table-mode and training-kernel entry points ----
@@ -266,7 +261,7 @@ int anh_op_conv_forward(int precision, const anh_conv_desc* d, int n, int h_in, 
         const DType dt = precision == ANH_BF16 ? DT_BF16 : DT_F32;
         const int h_out = out_dim(*d, h_in), w_out = out_dim(*d, w_in);
         ANH_REQUIRE(h_out >= 1 && w_out >= 1, "input too small");
-        Stream st;
+        OpStream st;
         OpSource in;
         make_source(in, a, b, (size_t)n * h_in * w_in * d->cin, d->cin, dt);
         Filters f;
@@ -299,7 +294,7 @@ int anh_op_conv_backward_data(int precision, const anh_conv_desc* d, int n, int 
         const DType dt = precision == ANH_BF16 ? DT_BF16 : DT_F32;
         const int h_out = out_dim(*d, h_in), w_out = out_dim(*d, w_in);
         ANH_REQUIRE(h_out >= 1 && w_out >= 1, "input too small");
-        Stream st;
+        OpStream st;
         DevBuf g, out;
         upload(g, dy, (size_t)n * h_out * w_out * d->cout, dt);
         Filters f;
@@ -328,7 +323,7 @@ int anh_op_conv_backward_filter(int precision, const anh_conv_desc* d, int n, in
         const DType dt = precision == ANH_BF16 ? DT_BF16 : DT_F32;
         const int h_out = out_dim(*d, h_in), w_out = out_dim(*d, w_in);
         ANH_REQUIRE(h_out >= 1 && w_out >= 1, "input too small");
-        Stream st;
+        OpStream st;
         OpSource in;
         make_source(in, a, b, (size_t)n * h_in * w_in * d->cin, d->cin, dt);
         DevBuf g, out, scratch;
@@ -368,7 +363,7 @@ int anh_op_conv_forward_stats(int precision, const anh_conv_desc* d, int n, int 
         const DType dt = precision == ANH_BF16 ? DT_BF16 : DT_F32;
         const int h_out = out_dim(*d, h_in), w_out = out_dim(*d, w_in);
         ANH_REQUIRE(h_out >= 1 && w_out >= 1, "input too small");
-        Stream st;
+        OpStream st;
         OpSource in;
         make_source(in, a, b, (size_t)n * h_in * w_in * d->cin, d->cin, dt);
         Filters f;
@@ -396,14 +391,7 @@ int anh_op_conv_forward_stats(int precision, const anh_conv_desc* d, int n, int 
         }
         HIP_CHECK(hipStreamSynchronize(st.s));
         download(out, y, out_elems, dt);
-        std::vector<double> p((size_t)blocks * 2 * d->cout);
-        HIP_CHECK(hipMemcpy(p.data(), partials.p, p.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int ch = 0; ch < d->cout; ++ch)
-            for (int which = 0; which < 2; ++which) {
-                double s = 0;
-                for (int k = 0; k < blocks; ++k) s += p[((size_t)ch * 2 + which) * blocks + k];
-                sums[ch * 2 + which] = s;
-            }
+        sum_partials(partials, blocks, d->cout, sums);
         if (fused) *fused = fused_here;
     });
 }
@@ -417,7 +405,7 @@ int anh_op_conv_backward_data_bn(int precision, const anh_conv_desc* d, int n, i
         const DType dt = precision == ANH_BF16 ? DT_BF16 : DT_F32;
         const int h_out = out_dim(*d, h_in), w_out = out_dim(*d, w_in);
         ANH_REQUIRE(h_out >= 1 && w_out >= 1, "input too small");
-        Stream st;
+        OpStream st;
         DevBuf g, out, yp, sc, sf, mn, is, partials, coef;
         upload(g, dy, (size_t)n * h_out * w_out * d->cout, dt);
         Filters f;
@@ -452,14 +440,7 @@ int anh_op_conv_backward_data_bn(int precision, const anh_conv_desc* d, int n, i
         }
         HIP_CHECK(hipStreamSynchronize(st.s));
         download(out, dx, out_elems, dt);
-        std::vector<double> p((size_t)blocks * 2 * d->cin);
-        HIP_CHECK(hipMemcpy(p.data(), partials.p, p.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int ch = 0; ch < d->cin; ++ch)
-            for (int which = 0; which < 2; ++which) {
-                double s = 0;
-                for (int k = 0; k < blocks; ++k) s += p[((size_t)ch * 2 + which) * blocks + k];
-                sums[ch * 2 + which] = s;
-            }
+        sum_partials(partials, blocks, d->cin, sums);
         if (fused) *fused = fused_here;
     });
 }
@@ -472,7 +453,7 @@ int anh_op_conv_backward_filter_bn(int precision, const anh_conv_desc* d, int n,
         const DType dt = precision == ANH_BF16 ? DT_BF16 : DT_F32;
         const int h_out = out_dim(*d, h_in), w_out = out_dim(*d, w_in);
         ANH_REQUIRE(h_out >= 1 && w_out >= 1, "input too small");
-        Stream st;
+        OpStream st;
         DevBuf img, da, yy, sc, sf, mn, is, cf, out, scratch;
         const size_t img_bytes = (size_t)n * h_in * w_in * d->cin;
         img.reserve(img_bytes);
@@ -485,7 +466,7 @@ int anh_op_conv_backward_filter_bn(int precision, const anh_conv_desc* d, int n,
         const size_t nw = (size_t)kk * d->cin * d->cout;
         out.reserve(nw * 4);
         WgradArgs w;
-        w.src.kind = SRC_IMAGE; w.src.img = img.as<uint8_t>(); w.src.img_h = h_in; w.src.img_w = w_in; w.src.img_sample_stride = (int64_t)h_in * w_in * d->cin;
+        w.src = image_source(img.as<uint8_t>(), h_in, w_in, d->cin);
         w.dy = da.p; w.dy_dtype = dt;
         w.n = n; w.h_in = h_in; w.w_in = w_in; w.c_in = d->cin; w.h_out = h_out; w.w_out = w_out; w.c_out = d->cout;
         w.k = d->k; w.stride = d->stride; w.pad = d->pad; w.gather = d->type;
@@ -522,7 +503,7 @@ int anh_op_conv_backward_filter_bn(int precision, const anh_conv_desc* d, int n,
 int anh_op_bn_fold(anh_op_bn_layer* layers, int n_jobs, uint64_t spread_seed) {
     return guarded([&] {
         ANH_REQUIRE(layers && n_jobs >= 1 && n_jobs <= 16, "1 to 16 fold jobs");
-        Stream st;
+        OpStream st;
         unsigned long long state = spread_seed;
         std::vector<Table> tabs(n_jobs);
         std::vector<LayerDev> dev(n_jobs);
@@ -545,7 +526,7 @@ int anh_op_bn_forward_stats(int precision, const float* y, anh_op_bn_layer* laye
         const DType dt = precision == ANH_BF16 ? DT_BF16 : DT_F32;
         const anh_op_bn_layer& L = *layer;
         const int64_t pixels = (int64_t)L.pixels;
-        Stream st;
+        OpStream st;
         LayerDev dev;
         dev.prepare(L);
         DevBuf yy, partials;
@@ -573,7 +554,7 @@ int anh_op_conv_forward_stats_table(int precision, const anh_conv_desc* d, int n
         const DType dt = precision == ANH_BF16 ? DT_BF16 : DT_F32;
         const int h_out = out_dim(*d, h_in), w_out = out_dim(*d, w_in);
         ANH_REQUIRE(h_out >= 1 && w_out >= 1, "input too small");
-        Stream st;
+        OpStream st;
         unsigned long long state = 0x7ab1e5ull + (unsigned long long)d->cout;
         BnSource in;
         DevBuf img;
@@ -582,8 +563,8 @@ int anh_op_conv_forward_stats_table(int precision, const anh_conv_desc* d, int n
         if (image) {
             img.reserve(in_elems);
             HIP_CHECK(hipMemcpy(img.p, image, in_elems, hipMemcpyHostToDevice));
-            c.src.kind = SRC_IMAGE; c.src.dtype = dt; c.src.img = img.as<uint8_t>(); c.src.img_h = h_in; c.src.img_w = w_in;
-            c.src.img_sample_stride = (int64_t)h_in * w_in * d->cin;
+            c.src = image_source(img.as<uint8_t>(), h_in, w_in, d->cin);
+            c.src.dtype = dt;
         } else {
             in.make(a, b, in_elems, d->cin, dt, state);
             c.src = in.src;
@@ -626,7 +607,7 @@ int anh_op_conv_backward_data_bn_table(int precision, const anh_conv_desc* d, in
         const int h_out = out_dim(*d, h_in), w_out = out_dim(*d, w_in);
         ANH_REQUIRE(h_out >= 1 && w_out >= 1, "input too small");
         ANH_REQUIRE(bn_table_mode_ok(d->cin), "no table mode at this width");
-        Stream st;
+        OpStream st;
         DevBuf g, out, yp, sc, sf, mn, is, gm, dg, db, cf;
         upload(g, dy, (size_t)n * h_out * w_out * d->cout, dt);
         Filters f;
@@ -689,7 +670,7 @@ int anh_op_bn_backward(int precision, anh_op_bn_bwd* op) {
         ANH_REQUIRE(!apply || ((coef_made || o.coef_in) && o.dy), "the apply stage needs coefficients and dy");
         const size_t elems = (size_t)o.pixels * o.c;
         const size_t es = dt == DT_BF16 ? 2 : 4;
-        Stream st;
+        OpStream st;
         DevBuf da, yy, mn, is, sc, sf, gm, dg, db, cf, partials, dyb, hg, hw;
         if (head) { da.reserve(elems * es); HIP_CHECK(hipMemset(da.p, 0xff, elems * es)); }
         else upload(da, o.da, elems, dt);
@@ -747,7 +728,7 @@ int anh_op_head_train(int precision, anh_op_head* op) {
         const DType dt = precision == ANH_BF16 ? DT_BF16 : DT_F32;
         const int C = 32, K = o.k;
         const size_t elems = (size_t)o.pixels * C;
-        Stream st;
+        OpStream st;
         unsigned long long state = 0x4ead5ull + (unsigned long long)K;
         BnSource in;
         in.make(o.a, o.b, elems, C, dt, state);
@@ -823,7 +804,7 @@ int anh_op_loss(const float* logits, const uint16_t* labels, const float* weight
                 float* dlogits, double* loss, float* dbias, int* error_flag) {
     return guarded([&] {
         ANH_REQUIRE(logits && labels && weights && dlogits && loss && dbias && pixels >= 1 && k >= 1, "null argument");
-        Stream st;
+        OpStream st;
         DevBuf z, lab, wgt, g, partials, ls, ls32, db, err;
         upload_f32(z, logits, (size_t)pixels * k);
         lab.reserve((size_t)pixels * 2);

@@ -12,10 +12,33 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-VARIANTS = ["natural", "natural_nocpu", "no_pinned", "no_waitstream", "net_first", "net_first_nosync", "handle_last", "workaround"]
+VARIANTS = ["natural", "natural_nocpu", "no_pinned", "no_waitstream", "net_first", "net_first_nosync", "handle_last", "workaround",
+            "trainer_two_replicas_nosync"]
+
+
+def trainer_flow():
+    """A two-replica trainer (devices 0,0) dropped right after StartTraining, with the uploads, both replicas' steps and the
+    all-reduce still in flight: the handle's tear-down (workers, every engine drained under its device, then the staging sets) must cope."""
+    import numpy as np
+    import annonet_amd as aa
+    aa.set_devices([0, 0])
+    t = aa.TrainingNet(1, 3, aa.ANH_BF16, seed=3)
+    t.Initialize()
+    t.SetNetWidth(0.25, 4)
+    t.SetClassCount(3)
+    t.SetLearningRate(0.05)
+    assert t.replicas() == 2
+    rng = np.random.default_rng(0)
+    img = rng.integers(0, 256, (4, 31, 31, 3), dtype=np.uint8)
+    lab = rng.integers(0, 3, (4, 31, 31)).astype(np.uint16)
+    t.StartTraining(list(img), [aa.set_weights(l, 0.5, 0.5) for l in lab])
+    del t
+    print("line printed", flush=True)
 
 
 def flow(variant):
+    if variant == "trainer_two_replicas_nosync":
+        return trainer_flow()
     import numpy as np
     import torch
     import annonet_amd as aa
