@@ -135,6 +135,10 @@ _SIGNATURES = {  # ConvDesc / OpInput are defined above
     "anh_runtime_forward_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "anh_infer": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), _P, _P]),
     "anh_infer_device": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(TilingParams), C.POINTER(Tile), C.c_size_t, _P, _P]),
+    "anh_infer_batch": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), C.POINTER(_P), C.POINTER(_P)]),
+    "anh_infer_batch_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(TilingParams), _P, _P]),
+    "anh_labels_from_logits_device": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P, _P]),
+    "anh_infer_batch_plan": (C.c_int, [C.POINTER(Tile), C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_int)), C.POINTER(C.POINTER(C.c_int)), C.POINTER(C.c_size_t)]),
     "anh_argmax_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "anh_scaled_dims": (C.c_int, [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "anh_resize_image_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),

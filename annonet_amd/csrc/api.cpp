@@ -286,16 +286,21 @@ bool detection_requested(const double* detection_levels, int K) {
     if (detection_levels) for (int k = 0; k < K; ++k) { ANH_REQUIRE(detection_levels[k] >= 0.0, "detection levels must be >= 0"); if (detection_levels[k] > 0.0) any = true; }
     return any;
 }
-// detection-level filter (annonet_infer.cpp:187-239), on the resident planes (stage_blended) and label map (stage_result) of h x w.
+// detection-level filter (annonet_infer.cpp:187-239), on resident planes [K][h][w] and their label map of h x w.
 // Seeds are looked up at (row, col): the reference stores (r, c) but reads (point.y(), point.x()) — transposed (:210 vs :222); see DESIGN.md.
-void apply_detection_levels(Engine& e, const double* levels, int K, int h, int w) {
+size_t detection_scratch_bytes(size_t plane, int K) { return plane + (size_t)K * sizeof(double) + 64; }   // flags, levels, the change counter
+void apply_detection_levels(Engine& e, const double* levels, int K, int h, int w, const float* d_blended, uint16_t* d_labels) {
     const size_t plane = (size_t)h * w;
-    e.stage_out.reserve(plane + (size_t)K * sizeof(double) + 64);
+    e.stage_out.reserve(detection_scratch_bytes(plane, K));
     uint8_t* flags = e.stage_out.as<uint8_t>();
     double* d_det = reinterpret_cast<double*>(flags + ((plane + 15) / 16) * 16);
     int* d_changed = reinterpret_cast<int*>(d_det + K);
     HIP_CHECK(hipMemcpyAsync(d_det, levels, (size_t)K * sizeof(double), hipMemcpyHostToDevice, e.stream));
-    run_detection_filter(e.stage_blended.as<float>(), e.stage_result.as<uint16_t>(), K, h, w, d_det, flags, d_changed, e.stream);
+    run_detection_filter(d_blended, d_labels, K, h, w, d_det, flags, d_changed, e.stream);
+}
+// ... on the handle's stage buffers (anh_infer, anh_infer_scaled)
+void apply_detection_levels(Engine& e, const double* levels, int K, int h, int w) {
+    apply_detection_levels(e, levels, K, h, w, e.stage_blended.as<float>(), e.stage_result.as<uint16_t>());
 }
 }  // namespace
 
@@ -711,6 +716,95 @@ int anh_infer(anh_runtime* h, const uint8_t* image, int height, int width, const
         HIP_CHECK(hipMemcpyAsync(result, e.stage_result.p, plane * 2, hipMemcpyDeviceToHost, e.stream));
         if (blended_out) HIP_CHECK(hipMemcpyAsync(blended_out, e.stage_blended.p, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
         e.synchronize();
+    });
+}
+
+// ---- annonet_infer() over several images of one size (Engine::infer_batch_device) ----
+int anh_infer_batch_device(anh_runtime* h, const uint8_t* d_images, int n, int height, int width, const double* gains, const anh_tiling_params* tiling,
+                           uint16_t* d_results, float* d_blended) {
+    return guarded([&] {
+        ANH_REQUIRE(n >= 1, "infer_batch: the batch needs at least one image");
+        ANH_REQUIRE(h && d_images && d_results, "null argument");
+        ANH_REQUIRE(height >= 1 && width >= 1, "empty image");
+        DeviceScope scope(h->reps.device_of(0));
+        h->reps.engine(0).infer_batch_device(d_images, n, height, width, gains, tiles_for(tiling, width, height), d_results, d_blended);
+    });
+}
+
+int anh_infer_batch(anh_runtime* h, const uint8_t* const* images, int n, int height, int width, const double* gains, const double* detection_levels,
+                    const anh_tiling_params* tiling, uint16_t* const* results, float* const* blended_out) {
+    return guarded([&] {
+        ANH_REQUIRE(n >= 1, "infer_batch: the batch needs at least one image");
+        ANH_REQUIRE(images && results, "infer_batch: null image or result list");
+        ANH_REQUIRE(h, "null handle");
+        ANH_REQUIRE(height >= 1 && width >= 1, "empty image");
+        for (int i = 0; i < n; ++i) ANH_REQUIRE(images[i] && results[i], "infer_batch: null image or result");
+        const size_t R = h->reps.size();
+        if ((size_t)n < R) {   // fewer images than replicas: image by image, as anh_infer serves them
+            for (int i = 0; i < n; ++i) {
+                const int rc = anh_infer(h, images[i], height, width, gains, detection_levels, tiling, results[i], blended_out ? blended_out[i] : nullptr);
+                if (rc != ANH_OK) fail(rc, g_error);
+            }
+            return;
+        }
+        const int K = h->reps.engine(0).spec.cfg.classes, C = h->reps.engine(0).spec.cfg.in_channels;
+        const size_t plane = (size_t)height * width;
+        const std::vector<anh_tile> tiles = tiles_for(tiling, width, height);
+        const bool use_det = detection_requested(detection_levels, K);
+        // every replica takes a contiguous share of the images; an image is computed wholly on one replica, so nothing is exchanged
+        h->reps.each([&](size_t r, Engine& e) {
+            int64_t lo = 0, hi = 0;
+            shard_range((int64_t)n, (int)R, (int)r, lo, hi);
+            const int m = (int)(hi - lo);
+            if (m <= 0) return;
+            bool planes = use_det;   // the filter reads the planes
+            if (blended_out) for (int64_t i = lo; i < hi; ++i) planes = planes || blended_out[i] != nullptr;
+            e.stage_image.reserve((size_t)m * plane * C);
+            e.stage_result.reserve((size_t)m * plane * 2);
+            if (planes) e.stage_blended.reserve((size_t)m * plane * K * 4);
+            if (use_det) e.stage_out.reserve(detection_scratch_bytes(plane, K));   // (the filter's scratch: reserved with the rest, before the first kernel)
+            for (int i = 0; i < m; ++i)
+                HIP_CHECK(hipMemcpyAsync(e.stage_image.as<uint8_t>() + (size_t)i * plane * C, images[lo + i], plane * C, hipMemcpyHostToDevice, e.stream));
+            float* d_planes = planes ? e.stage_blended.as<float>() : nullptr;
+            uint16_t* d_labels = e.stage_result.as<uint16_t>();
+            e.infer_batch_device(e.stage_image.as<uint8_t>(), m, height, width, gains, tiles, d_labels, d_planes);
+            for (int i = 0; i < m; ++i) {
+                if (use_det) apply_detection_levels(e, detection_levels, K, height, width, d_planes + (size_t)i * K * plane, d_labels + (size_t)i * plane);
+                HIP_CHECK(hipMemcpyAsync(results[lo + i], d_labels + (size_t)i * plane, plane * 2, hipMemcpyDeviceToHost, e.stream));
+                if (blended_out && blended_out[lo + i])
+                    HIP_CHECK(hipMemcpyAsync(blended_out[lo + i], d_planes + (size_t)i * K * plane, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
+            }
+            e.synchronize();
+        });
+    });
+}
+
+int anh_labels_from_logits_device(anh_runtime* h, const float* d_logits, int count, int classes, int win_height, int win_width, int top, int left,
+                                  int height, int width, const double* gains, uint16_t* d_result) {
+    return guarded([&] {
+        ANH_REQUIRE(h && d_logits && d_result, "null argument");
+        ANH_REQUIRE(count >= 1 && classes >= 1, "labels_from_logits: empty batch");
+        DeviceScope scope(h->reps.device_of(0));
+        Engine& e = h->reps.engine(0);
+        e.labels_from_logits(d_logits, count, classes, win_height, win_width, top, left, height, width, e.upload_gains(gains, classes), d_result);
+    });
+}
+
+int anh_infer_batch_plan(const anh_tile* tiles, size_t n_tiles, int n_images, int levels, int cap, int** pairs, int** batch_sizes, size_t* n_batches) {
+    return guarded([&] {
+        ANH_REQUIRE(tiles && n_tiles >= 1 && pairs && batch_sizes && n_batches, "null argument");
+        ANH_REQUIRE(n_images >= 1 && cap >= 1 && levels >= 0 && levels <= 3, "infer_batch_plan: bad argument");
+        const auto plan = infer_batch_plan(std::vector<anh_tile>(tiles, tiles + n_tiles), n_images, levels, [cap](int, int) { return cap; });
+        const size_t total = n_tiles * (size_t)n_images;
+        int* p = (int*)std::malloc(total * 2 * sizeof(int));
+        int* b = (int*)std::malloc(std::max<size_t>(1, plan.size()) * sizeof(int));
+        if (!p || !b) { std::free(p); std::free(b); fail(ANH_ERR_OOM, "host allocation failed"); }
+        size_t k = 0;
+        for (size_t i = 0; i < plan.size(); ++i) {
+            b[i] = (int)plan[i].size();
+            for (const TileSample& s : plan[i]) { p[2 * k] = s.image; p[2 * k + 1] = s.tile; ++k; }
+        }
+        *pairs = p; *batch_sizes = b; *n_batches = plan.size();
     });
 }
 

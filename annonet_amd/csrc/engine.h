@@ -117,16 +117,34 @@ class Engine {
     static constexpr int kMaxTileBatch = 16;   // Src::img_win holds 16 windows (4096^2 image, 25 tiles of 1024^2: batches of 8+8+8+1 / 7+6+6+6 / 9+8+8 / 13+12 / 25: 3,838 / 3,865 / 3,917 / 3,960 / 3,938 Mpx/s)
     void infer_tile(const anh_tile& t, const uint8_t* d_image, int H, int W, float* d_blended);
     void infer_tiles(const anh_tile* ts, int count, const uint8_t* d_image, int H, int W, float* d_blended);
+    // A batch whose samples are (image, tile) pairs over images of one size: sample i is tile ts[i] of image images[i], which lives
+    // image_stride bytes per index behind d_images and blends into the planes plane_stride floats per index behind d_blended.
+    // images == nullptr: every sample is a tile of the one image at d_images (infer_tiles).  d_direct_labels: every sample is a whole image
+    // (single tile, consecutive images) and the labels are taken straight from the batch's logits — no planes are written.
+    void infer_samples(const anh_tile* const* ts, const int* images, int count, const uint8_t* d_images, int64_t image_stride, int H, int W,
+                       float* d_blended, int64_t plane_stride, uint16_t* d_direct_labels = nullptr, const double* d_gains = nullptr);
+    // whether a batch of `count` windows of h x w leaves its logits in memory (fp32 mode, the generic head, bf16 with the head in the
+    // conv epilogue) rather than on chip (the fused head + blend kernel); reserves the batch's layer tensors and logits
+    bool batch_logits_in_memory(int count, int h, int w);
+    struct TailForm { bool fuse_head = false, head_epi = false; HeadBlendArgs hb; };
+    TailForm plan_tail_form(const Src& image, int count, int h, int w);
+    // annonet_infer() over n images of one size, resident as [n][H][W][C]: labels [n][H][W], planes [n][K][H][W] (d_blended may be null:
+    // planes of the engine's own are used where the labels cannot come straight from the logits).  `tiles` is the complete tiling of one image.
+    void infer_batch_device(const uint8_t* d_images, int n, int H, int W, const double* gains_host, const std::vector<anh_tile>& tiles,
+                            uint16_t* d_labels, float* d_blended);
+    void labels_from_logits(const float* d_logits, int count, int k, int win_h, int win_w, int top, int left, int H, int W, const double* d_gains, uint16_t* d_labels);
+    DevBuf batch_planes;
     bool infer_post = false;   // this inference pass stores post-activation tensors (choose_inference_form)
     ConvArgs forward_conv_args(int li, const Src& image, bool training_pass, float* d_out_nchw) const;
     void choose_inference_form(const Src& image);
     int tile_batch(int h, int w) const;
-    const double* upload_gains(const double* gains_host);   // -> device pointer (or nullptr)
+    const double* upload_gains(const double* gains_host, int k = 0);   // -> device pointer (or nullptr); k doubles, 0 = the net's class count
     void argmax_rows(const float* d_blended, int H, int W, int row0, int row1, const double* gains_host, uint16_t* d_labels);   // find_label over rows [row0, row1)
     // whole_image: `tiles` is the image's COMPLETE tiling (then only the frames the blends accumulate into are cleared first)
     void infer_device(const uint8_t* d_image, int H, int W, const double* gains_host, const std::vector<anh_tile>& tiles,
                       uint16_t* d_labels, float* d_blended, bool whole_image = false);
     DevBuf zero_rects; int zero_rects_n = 0; uint64_t zero_rects_key = 0;   // the frames of the last whole-image tiling
+    void prepare_zero_rects(int H, int W, const std::vector<anh_tile>& tiles);
 
     // ANH_STEP_GRAPH=1: the backward pass behind the head replayed as a captured HIP graph (Engine::backward)
     struct StepGraph { uint64_t key; int eager_runs; hipGraphExec_t exec; };

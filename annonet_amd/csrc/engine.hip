@@ -914,13 +914,29 @@ void Engine::infer_tile(const anh_tile& t, const uint8_t* d_image, int H, int W,
 // (annonet_infer.cpp:116-164), so the result does not depend on the batch size.
 void Engine::infer_tiles(const anh_tile* ts, int count, const uint8_t* d_image, int H, int W, float* d_blended) {
     ANH_REQUIRE(count >= 1 && count <= kMaxTileBatch, "infer_tiles: batch size out of range");
+    const anh_tile* list[kMaxTileBatch];
+    for (int i = 0; i < count; ++i) list[i] = ts + i;
+    infer_samples(list, nullptr, count, d_image, 0, H, W, d_blended, 0);
+}
+
+void Engine::infer_samples(const anh_tile* const* tps, const int* images, int count, const uint8_t* d_image, int64_t image_stride, int H, int W,
+                           float* d_blended, int64_t plane_stride, uint16_t* d_direct_labels, const double* d_gains) {
+    ANH_REQUIRE(count >= 1 && count <= kMaxTileBatch, "infer_tiles: batch size out of range");
     const int K = spec.cfg.classes;
+    anh_tile ts[kMaxTileBatch];
+    for (int i = 0; i < count; ++i) ts[i] = *tps[i];
+    auto planes_of = [&](int i) { return images ? d_blended + (size_t)images[i] * plane_stride : d_blended; };
     const TileWindow win = tile_window(ts[0], spec.cfg.levels);
     Src image;
     image.kind = SRC_IMAGE;
     image.img = d_image; image.img_h = H; image.img_w = W; image.img_left = win.left; image.img_top = win.top;
-    if (count > 1) {
-        image.img_nwin = count;   // (img_sample_stride stays 0: the samples are windows of the same image)
+    if (images) {   // sample i reads image images[i]
+        image.img_sample_stride = image_stride;
+        image.img_nidx = count;
+        for (int i = 0; i < count; ++i) image.img_idx[i] = images[i];
+    }
+    if (count > 1 || images) {
+        image.img_nwin = count;   // (one image: img_sample_stride stays 0, the samples are windows of the same image)
         for (int i = 0; i < count; ++i) {
             const TileWindow wi = tile_window(ts[i], spec.cfg.levels);
             ANH_REQUIRE(wi.height == win.height && wi.width == win.width, "infer_tiles: tiles of one batch must have equal windows");
@@ -929,23 +945,13 @@ void Engine::infer_tiles(const anh_tile* ts, int count, const uint8_t* d_image, 
     }
     // bf16 mode: the 1x1 head and the blend run as one kernel over the last hidden tensor (the tile's logits stay on chip)
     const anh_layer_desc& head = spec.layers.back();
-    HeadBlendArgs hb;
-    hb.src = layer_source((int)spec.layers.size() - 1, image); hb.c_in = head.cin; hb.k = head.cout;
-    const bool fuse_head = !training && head.k == 1 && head.has_bias && head.in_a >= 0 && head_blend_supported(hb);
-    bool head_epi = false;   // the head rides in the epilogue of the last hidden layer's conv: its logits, not its activation, go to memory
+    const TailForm tail = plan_tail_form(image, count, win.height, win.width);
+    HeadBlendArgs hb = tail.hb;
+    const bool fuse_head = tail.fuse_head, head_epi = tail.head_epi;
     DevBuf& tout = tile_out;
     if (fuse_head) {
         prof.start_pass();
-        plan_dims(count, win.height, win.width);
-        choose_inference_form(image);
         const int hl = head.in_a;
-        if (head.in_b < 0 && hl == (int)spec.layers.size() - 2) {
-            int readers = 0;
-            for (const anh_layer_desc& X : spec.layers) readers += (X.in_a == hl) + (X.in_b == hl);
-            ConvArgs probe = forward_conv_args(hl, image, false, nullptr);
-            probe.head_k = head.cout;
-            head_epi = readers == 1 && conv_head_in_epilogue_ok(probe);
-        }
         if (head_epi) {
             tout.reserve((size_t)count * K * win.height * win.width * 4);
             head_epi_layer = hl; head_epi_out = tout.as<float>();
@@ -955,6 +961,15 @@ void Engine::infer_tiles(const anh_tile* ts, int count, const uint8_t* d_image, 
     } else {
         tout.reserve((size_t)count * K * win.height * win.width * 4);
         forward_inference(image, count, win.height, win.width, tout.as<float>());
+    }
+    if (d_direct_labels) {   // whole images: a tile assigns every pixel, so the planes would be a copy of these logits
+        ANH_REQUIRE(images && !(fuse_head && !head_epi), "internal: labels from the logits of a batch whose logits are not in memory");
+        for (int i = 0; i < count; ++i) {
+            const TileWindow wi = tile_window(ts[i], spec.cfg.levels);
+            ANH_REQUIRE(images[i] == images[0] + i && wi.left == win.left && wi.top == win.top, "internal: labels from logits need whole consecutive images");
+        }
+        labels_from_logits(tout.as<float>(), count, K, win.height, win.width, win.top, win.left, H, W, d_gains, d_direct_labels + (size_t)images[0] * H * W);
+        return;
     }
     const size_t es = elem_size(dtype);
     const hipStream_t bs = stream;   // (a batch's blends on a second stream beside the next batch's convs measured no gain in round 4: the persistent conv kernels hold every CU)
@@ -967,6 +982,7 @@ void Engine::infer_tiles(const anh_tile* ts, int count, const uint8_t* d_image, 
         for (int i = 0; i < count; ++i) {
             const TileWindow wi = tile_window(ts[i], spec.cfg.levels);
             bb.left[i] = wi.left; bb.top[i] = wi.top;
+            if (images) { bb.image[i] = images[i]; bb.plane_off[i] = (int64_t)images[i] * plane_stride; }
             const anh_rect &f = ts[i].full_rect, &u = ts[i].unique_rect;
             bb.full[i][0] = (int)f.left; bb.full[i][1] = (int)f.top; bb.full[i][2] = (int)f.right; bb.full[i][3] = (int)f.bottom;
             bb.unique[i][0] = (int)u.left; bb.unique[i][1] = (int)u.top; bb.unique[i][2] = (int)u.right; bb.unique[i][3] = (int)u.bottom;
@@ -982,7 +998,7 @@ void Engine::infer_tiles(const anh_tile* ts, int count, const uint8_t* d_image, 
         const anh_tile& t = ts[i];
         const TileWindow wi = tile_window(t, spec.cfg.levels);
         BlendArgs b;
-        b.logits_nchw = (fuse_head && !head_epi) ? nullptr : tout.as<float>() + (size_t)i * K * win.height * win.width; b.blended = d_blended;
+        b.logits_nchw = (fuse_head && !head_epi) ? nullptr : tout.as<float>() + (size_t)i * K * win.height * win.width; b.blended = planes_of(i);
         b.k = K; b.tile_h = wi.height; b.tile_w = wi.width; b.tile_left = wi.left; b.tile_top = wi.top;
         b.img_h = H; b.img_w = W;
         b.full[0] = t.full_rect.left; b.full[1] = t.full_rect.top; b.full[2] = t.full_rect.right; b.full[3] = t.full_rect.bottom;
@@ -1023,12 +1039,39 @@ int Engine::tile_batch(int h, int w) const {
     return std::max(1, std::min(kMaxTileBatch, batch));
 }
 
-const double* Engine::upload_gains(const double* gains_host) {
+const double* Engine::upload_gains(const double* gains_host, int k) {
     if (!gains_host) return nullptr;
-    const int K = spec.cfg.classes;
+    const int K = k > 0 ? k : spec.cfg.classes;
     gains_dev.reserve((size_t)K * sizeof(double));
     HIP_CHECK(hipMemcpyAsync(gains_dev.p, gains_host, (size_t)K * sizeof(double), hipMemcpyHostToDevice, stream));
     return gains_dev.as<double>();
+}
+
+// the frames between the tiles' full and unique rectangles as a device list (kept while the tiling stays the same)
+void Engine::prepare_zero_rects(int H, int W, const std::vector<anh_tile>& tiles) {
+    uint64_t key = 1469598103934665603ull;
+    auto mix = [&key](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
+    mix((uint64_t)H); mix((uint64_t)W); mix((uint64_t)tiles.size());
+    for (const anh_tile& t : tiles) for (long v : {t.full_rect.left, t.full_rect.top, t.full_rect.right, t.full_rect.bottom, t.unique_rect.left, t.unique_rect.top, t.unique_rect.right, t.unique_rect.bottom}) mix((uint64_t)v);
+    if (key != zero_rects_key || !zero_rects.p) {
+        std::vector<anh_rect> frames;
+        auto add = [&](long l, long t, long r, long b) {
+            l = std::max(l, 0L); t = std::max(t, 0L); r = std::min(r, (long)W - 1); b = std::min(b, (long)H - 1);
+            if (l <= r && t <= b) frames.push_back(anh_rect{l, t, r, b});
+        };
+        for (const anh_tile& t : tiles) {
+            const anh_rect &f = t.full_rect, &u = t.unique_rect;
+            add(f.left, f.top, f.right, u.top - 1);        // above the unique rectangle
+            add(f.left, u.bottom + 1, f.right, f.bottom);  // below
+            add(f.left, u.top, u.left - 1, u.bottom);      // left of it
+            add(u.right + 1, u.top, f.right, u.bottom);    // right of it
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));   // (a previous image's clear may still read the old list)
+        zero_rects.reserve(std::max<size_t>(frames.size(), 1) * sizeof(anh_rect));
+        if (!frames.empty()) HIP_CHECK(hipMemcpy(zero_rects.p, frames.data(), frames.size() * sizeof(anh_rect), hipMemcpyHostToDevice));
+        zero_rects_n = (int)frames.size();
+        zero_rects_key = key;
+    }
 }
 
 void Engine::infer_device(const uint8_t* d_image, int H, int W, const double* gains_host, const std::vector<anh_tile>& tiles,
@@ -1042,35 +1085,16 @@ void Engine::infer_device(const uint8_t* d_image, int H, int W, const double* ga
     // list is the image's complete tiling only those frames need to be zero: 7 % of a 4096^2 image at 1024^2 tiles (14 MB of 201), 3.6 %
     // of a 16384^2 one — round 5; a tile list that is a replica's share leaves pixels no tile of it writes, so that path clears all.
     if (whole_image && tiles.size() > 1) {
-        uint64_t key = 1469598103934665603ull;
-        auto mix = [&key](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
-        mix((uint64_t)H); mix((uint64_t)W); mix((uint64_t)tiles.size());
-        for (const anh_tile& t : tiles) for (long v : {t.full_rect.left, t.full_rect.top, t.full_rect.right, t.full_rect.bottom, t.unique_rect.left, t.unique_rect.top, t.unique_rect.right, t.unique_rect.bottom}) mix((uint64_t)v);
-        if (key != zero_rects_key || !zero_rects.p) {
-            std::vector<anh_rect> frames;
-            auto add = [&](long l, long t, long r, long b) {
-                l = std::max(l, 0L); t = std::max(t, 0L); r = std::min(r, (long)W - 1); b = std::min(b, (long)H - 1);
-                if (l <= r && t <= b) frames.push_back(anh_rect{l, t, r, b});
-            };
-            for (const anh_tile& t : tiles) {
-                const anh_rect &f = t.full_rect, &u = t.unique_rect;
-                add(f.left, f.top, f.right, u.top - 1);        // above the unique rectangle
-                add(f.left, u.bottom + 1, f.right, f.bottom);  // below
-                add(f.left, u.top, u.left - 1, u.bottom);      // left of it
-                add(u.right + 1, u.top, f.right, u.bottom);    // right of it
-            }
-            HIP_CHECK(hipStreamSynchronize(stream));   // (a previous image's clear may still read the old list)
-            zero_rects.reserve(std::max<size_t>(frames.size(), 1) * sizeof(anh_rect));
-            if (!frames.empty()) HIP_CHECK(hipMemcpy(zero_rects.p, frames.data(), frames.size() * sizeof(anh_rect), hipMemcpyHostToDevice));
-            zero_rects_n = (int)frames.size();
-            zero_rects_key = key;
-        }
+        prepare_zero_rects(H, W, tiles);
         launch_zero_rects(d_blended, K, H, W, zero_rects.as<anh_rect>(), zero_rects_n, stream);
     } else if (!(whole_image && tiles.size() == 1))   // (a single tile assigns every pixel of the image: nothing to clear)
         launch_fill_zero(d_blended, (size_t)K * pixels * 4, stream);
     // consecutive tiles with equal input windows (all of them, on a regular tiling) run as batches
     // — as FEW batches as the cap allows, of equal size (25 tiles at a cap of 8 used to run as 8 + 8 + 8 + 1: every launch has a fixed
-    // prologue and tail, and the last batch paid them for one tile)
+    // prologue and tail, and the last batch paid them for one tile).  infer_batch_plan (hostlogic.cpp) cuts the batches of
+    // infer_batch_device by the same rule but spreads a remainder over the first batches (25 tiles at a cap of 8: 7+6+6+6 there, 7+7+7+4
+    // here).  The loop stays as it is on purpose: the single-image calls keep the launches they were measured and profiled with
+    // (bench.py's inference line, profiles/), and the result does not depend on the cut.
     for (size_t i = 0; i < tiles.size();) {
         const TileWindow w0 = tile_window(tiles[i], spec.cfg.levels);
         const size_t batch = (size_t)tile_batch(w0.height, w0.width);
@@ -1086,6 +1110,85 @@ void Engine::infer_device(const uint8_t* d_image, int H, int W, const double* ga
         i += run;
     }
     if (d_labels) argmax_rows(d_blended, H, W, 0, H, gains_host, d_labels);
+}
+
+void Engine::labels_from_logits(const float* d_logits, int count, int k, int win_h, int win_w, int top, int left, int H, int W, const double* d_gains, uint16_t* d_labels) {
+    const int tok = prof.begin(stream, "labels_from_logits", 0, (double)count * H * W * (k * 4.0 + 2.0));
+    launch_labels_from_logits(d_logits, count, k, win_h, win_w, top, left, H, W, d_gains, d_labels, stream);
+    prof.end(stream, tok);
+}
+
+// How the tail of an inference batch of `count` windows of h x w runs — decided in ONE place for the batch itself (infer_samples) and
+// for the reservations made ahead of it (batch_logits_in_memory).  fuse_head: the 1x1 head does not run as a conv of its own; then
+// head_epi: it rides in the epilogue of the last hidden layer's conv (its logits, not its activation, go to memory), else the fused
+// head + blend kernel keeps the logits on chip.  The decision needs the batch's planned dimensions and, for fuse_head, its inference
+// form: both are set here (plan_dims, choose_inference_form), as the forward that follows would set them.
+Engine::TailForm Engine::plan_tail_form(const Src& image, int count, int h, int w) {
+    const anh_layer_desc& head = spec.layers.back();
+    TailForm t;
+    t.hb.src = layer_source((int)spec.layers.size() - 1, image); t.hb.c_in = head.cin; t.hb.k = head.cout;
+    t.fuse_head = !training && head.k == 1 && head.has_bias && head.in_a >= 0 && head_blend_supported(t.hb);
+    if (!t.fuse_head) return t;
+    plan_dims(count, h, w);
+    choose_inference_form(image);
+    const int hl = head.in_a;
+    if (head.in_b < 0 && hl == (int)spec.layers.size() - 2) {
+        int readers = 0;
+        for (const anh_layer_desc& X : spec.layers) readers += (X.in_a == hl) + (X.in_b == hl);
+        ConvArgs probe = forward_conv_args(hl, image, false, nullptr);
+        probe.head_k = head.cout;
+        t.head_epi = readers == 1 && conv_head_in_epilogue_ok(probe);
+    }
+    return t;
+}
+
+bool Engine::batch_logits_in_memory(int count, int h, int w) {
+    ANH_REQUIRE(!training, "inference on a training net: take a runtime snapshot first");
+    Src image;
+    image.kind = SRC_IMAGE;
+    const TailForm tail = plan_tail_form(image, count, h, w);
+    if (!tail.fuse_head) plan_dims(count, h, w);   // (the plain forward plans them itself: here only to reserve the layer tensors)
+    const bool in_memory = !tail.fuse_head || tail.head_epi;
+    if (in_memory) tile_out.reserve((size_t)count * spec.cfg.classes * h * w * 4);
+    return in_memory;
+}
+
+// annonet_infer() over n images of one size in one call: the images' tile lists are concatenated and cut into forward batches that may
+// span image boundaries (infer_batch_plan), so a folder of frames that are one tile each runs the net with up to kMaxTileBatch frames per
+// launch.  Within an image the blends arrive in list order, as in infer_device: every image's planes and labels are those of the image alone.
+void Engine::infer_batch_device(const uint8_t* d_images, int n, int H, int W, const double* gains_host, const std::vector<anh_tile>& tiles,
+                                uint16_t* d_labels, float* d_blended) {
+    ANH_REQUIRE(n >= 1 && H >= 1 && W >= 1 && !tiles.empty(), "empty batch");
+    ANH_REQUIRE(d_images && d_labels, "null argument");
+    const int K = spec.cfg.classes, C = spec.cfg.in_channels;
+    const int64_t pixels = (int64_t)H * W;
+    prof.start_image();
+    const std::vector<std::vector<TileSample>> plan = infer_batch_plan(tiles, n, spec.cfg.levels, [this](int h, int w) { return tile_batch(h, w); });
+    // Everything the call needs is reserved before its first kernel is enqueued: a batch that cannot fit fails here with ANH_ERR_OOM.
+    bool direct = tiles.size() == 1 && !d_blended;   // labels straight from the logits: single-tile images, no planes asked for
+    int last_count = 0, last_h = 0, last_w = 0;
+    for (const std::vector<TileSample>& b : plan) {
+        const TileWindow w = tile_window(tiles[(size_t)b[0].tile], spec.cfg.levels);
+        if ((int)b.size() == last_count && w.height == last_h && w.width == last_w) continue;
+        last_count = (int)b.size(); last_h = w.height; last_w = w.width;
+        if (!batch_logits_in_memory(last_count, last_h, last_w)) direct = false;
+    }
+    if (!direct && !d_blended) { batch_planes.reserve((size_t)n * K * pixels * 4); d_blended = batch_planes.as<float>(); }
+    const double* d_gains = upload_gains(gains_host);
+    if (!direct && tiles.size() > 1) {   // only the frames are accumulated into (infer_device); a single tile assigns every pixel
+        prepare_zero_rects(H, W, tiles);
+        const int sets = std::max(1, 65535 / K);   // plane sets per launch (grid.y)
+        for (int i = 0; i < n; i += sets)
+            launch_zero_rects(d_blended + (size_t)i * K * pixels, K * std::min(sets, n - i), H, W, zero_rects.as<anh_rect>(), zero_rects_n, stream);
+    }
+    for (const std::vector<TileSample>& b : plan) {
+        const anh_tile* ts[kMaxTileBatch];
+        int images[kMaxTileBatch];
+        ANH_REQUIRE(b.size() <= (size_t)kMaxTileBatch, "internal: batch larger than the cap");
+        for (size_t i = 0; i < b.size(); ++i) { ts[i] = &tiles[(size_t)b[i].tile]; images[i] = b[i].image; }
+        infer_samples(ts, images, (int)b.size(), d_images, pixels * C, H, W, d_blended, (int64_t)K * pixels, direct ? d_labels : nullptr, d_gains);
+    }
+    if (!direct) labels_from_logits(d_blended, n, K, H, W, 0, 0, H, W, d_gains, d_labels);   // find_label over all n plane sets by one launch
 }
 
 void Engine::argmax_rows(const float* d_blended, int H, int W, int row0, int row1, const double* gains_host, uint16_t* d_labels) {

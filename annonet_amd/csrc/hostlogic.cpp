@@ -74,6 +74,30 @@ TileWindow tile_window(const anh_tile& t, int levels) {
     return w;
 }
 
+std::vector<std::vector<TileSample>> infer_batch_plan(const std::vector<anh_tile>& tiles, int n_images, int levels, const std::function<int(int, int)>& cap) {
+    std::vector<std::vector<TileSample>> batches;
+    if (tiles.empty() || n_images < 1) return batches;
+    std::vector<TileWindow> win;
+    for (const anh_tile& t : tiles) win.push_back(tile_window(t, levels));
+    const size_t T = tiles.size(), total = T * (size_t)n_images;
+    auto sample = [T](size_t i) { return TileSample{(int)(i / T), (int)(i % T)}; };
+    for (size_t i = 0; i < total;) {
+        const TileWindow& w0 = win[i % T];
+        const size_t batch = (size_t)std::max(1, cap(w0.height, w0.width));
+        size_t run = 1;
+        while (i + run < total && win[(i + run) % T].height == w0.height && win[(i + run) % T].width == w0.width) ++run;
+        const size_t n_batches = (run + batch - 1) / batch, base = run / n_batches, larger = run % n_batches;   // the first `larger` batches hold one more
+        for (size_t b = 0, done = 0; b < n_batches; ++b) {
+            const size_t size = base + (b < larger ? 1 : 0);
+            batches.emplace_back();
+            for (size_t j = done; j < done + size; ++j) batches.back().push_back(sample(i + j));
+            done += size;
+        }
+        i += run;
+    }
+    return batches;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // set_weights (annonet_train.h:20-83).  Per-crop histogram -> w_l = (avg/count_l)^class_weight, renormalised so that
 // the weights sum to total * (nr*nc/total)^image_weight.  "avg" divides by the histogram's *allocated* length

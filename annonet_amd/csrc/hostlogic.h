@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdint>
 #include <deque>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -25,6 +26,13 @@ int64_t ignore_large_nonzero_regions(uint16_t* labels, int nr, int nc, double by
 // Geometry of the net input cut around one tile (annonet_infer.cpp:46-66).
 struct TileWindow { int left, top, width, height; };
 TileWindow tile_window(const anh_tile& t, int levels);
+
+// The forward batches of an inference call over `n_images` images of one size, which share the tile list `tiles`: the images' lists are
+// concatenated image by image, and every run of consecutive entries with equal windows is cut into as few batches as cap(height, width)
+// of that window allows, of sizes that differ by at most one (the larger ones first).  A batch may span image boundaries.  One image
+// gives the batches Engine::infer_device runs wherever that rule's own sizes differ by at most one (it leaves the remainder to the last).
+struct TileSample { int image, tile; };
+std::vector<std::vector<TileSample>> infer_batch_plan(const std::vector<anh_tile>& tiles, int n_images, int levels, const std::function<int(int, int)>& cap);
 
 // dlib dnn_trainer's "shrink the learning rate when the loss stops decreasing" rule [UPSTREAM-UNVERIFIED].
 struct LrSchedule {

@@ -50,6 +50,11 @@ struct Src {
     int img_win[32] = {};
     __host__ __device__ int win_left(int n) const { return img_nwin ? img_win[2 * n] : img_left; }
     __host__ __device__ int win_top(int n) const { return img_nwin ? img_win[2 * n + 1] : img_top; }
+    // windows of SEVERAL images as the samples of a batch (Engine::infer_batch_device): sample n reads image img_idx[n], which lives at
+    // img + img_idx[n]*img_sample_stride; img_nidx = 0 means the identity (sample n reads image n)
+    int img_nidx = 0;
+    int img_idx[16] = {};
+    __host__ __device__ int image_of(int n) const { return img_nidx ? img_idx[n] : n; }
 };
 // SRC_IMAGE over whole samples: [n][h][w][channels] u8 on the device, the window at the image's origin
 inline Src image_source(const uint8_t* d, int h, int w, int channels) {
@@ -228,6 +233,9 @@ struct BlendBatchArgs {
     int left[16] = {}, top[16] = {};
     int full[16][4] = {}, unique[16][4] = {};   // l, t, r, b (inclusive, image coordinates)
     unsigned nbr[16] = {};                       // bit j: tile j's full rectangle intersects this tile's (launch_blend_batch fills it)
+    // a batch over several images of one size: tile i belongs to image image[i], whose planes start plane_off[i] floats behind `blended`;
+    // tiles of different images never meet ("the first tile of the batch that covers it" reads "the first tile of the same image")
+    int image[16] = {}; int64_t plane_off[16] = {};
 };
 bool blend_batch_ok(const BlendBatchArgs& a);   // the batch's unique rectangles are reached by no other tile of it (else: per-tile launches)
 void launch_blend_batch(BlendBatchArgs a, hipStream_t s);
@@ -243,6 +251,11 @@ bool conv_head_in_epilogue_ok(const ConvArgs& a);   // a = the conv of the last 
 void launch_head_blend(const HeadBlendArgs& a, hipStream_t s);
 void launch_argmax(const float* blended, int k, int64_t pixels, const double* gains_or_null, uint16_t* labels, hipStream_t s);
 void launch_argmax_range(const float* blended, int k, int64_t pixels, int64_t p0, int64_t p1, const double* gains_or_null, uint16_t* labels, hipStream_t s);
+// find_label straight from the logits of a batch whose samples are whole images: logits [count][k][win_h][win_w] (the net input window,
+// which starts at (left, top) in image coordinates and covers the image), labels [count][height][width]; pixel (y, x) of image s reads
+// logits[s][c][y - top][x - left].  With win = image and top = left = 0 this is launch_argmax over `count` plane sets in one launch.
+void launch_labels_from_logits(const float* logits, int count, int k, int win_h, int win_w, int top, int left, int height, int width,
+                               const double* gains_or_null, uint16_t* labels, hipStream_t s);
 
 void launch_fill_zero(void* p, size_t bytes, hipStream_t s);
 void launch_zero_rects(float* planes, int k, int H, int W, const anh_rect* d_rects, int n, hipStream_t s);   // zero n inclusive rectangles of every plane [k][H][W]

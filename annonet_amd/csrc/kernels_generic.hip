@@ -92,7 +92,7 @@ __device__ __forceinline__ float fetch1(const Src& s, int n, int y, int x, int h
     if (KIND == SRC_IMAGE) {
         const int sy = min(max(s.win_top(n) + y, 0), s.img_h - 1);
         const int sx = min(max(s.win_left(n) + x, 0), s.img_w - 1);
-        const uint8_t v = s.img[(size_t)n * s.img_sample_stride + ((size_t)sy * s.img_w + sx) * c_total + c];
+        const uint8_t v = s.img[(size_t)s.image_of(n) * s.img_sample_stride + ((size_t)sy * s.img_w + sx) * c_total + c];
         return (float)v * (1.0f / 256.0f);  // dlib input<>::to_tensor
     }
     const size_t i = (((size_t)n * h + y) * w + x) * c_total + c;
@@ -1559,7 +1559,7 @@ __global__ __launch_bounds__(256) void blend_batch_kernel(BlendBatchArgs a) {
     if (by < a.full[t][1] || by > a.full[t][3] || by < 0 || by >= a.img_h) return;
     if (bx < a.full[t][0] || bx > a.full[t][2] || bx < 0 || bx >= a.img_w) return;
     const size_t tile_px = (size_t)a.tile_h * a.tile_w, img_px = (size_t)a.img_h * a.img_w;
-    float* out = a.blended + (size_t)by * a.img_w + bx;
+    float* out = a.blended + a.plane_off[t] + (size_t)by * a.img_w + bx;
     if (bx >= a.unique[t][0] && bx <= a.unique[t][2] && by >= a.unique[t][1] && by <= a.unique[t][3]) {
         const float* in = a.logits + (size_t)t * a.k * tile_px + (size_t)y * a.tile_w + x;
         for (int k = 0; k < a.k; ++k) out[(size_t)k * img_px] = in[(size_t)k * tile_px];
@@ -1745,6 +1745,64 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* blended, int k
             if (value > best) { label = (uint16_t)c; best = value; }
         }
         labels[p] = label;
+    }
+}
+
+// labels of whole images straight from the logits of their (single) tiles (launch_labels_from_logits): find_label's arithmetic, shaped like
+// argmax_kernel.  A work item is a span of one label row: item 0 the row's head up to the first label whose address is 8-byte aligned
+// (taken from the pointer: a batch's maps may start anywhere), then spans of four (16-byte plane loads, one 8-byte label store while
+// k <= 8), the last one the row's tail.
+__global__ __launch_bounds__(256) void labels_from_logits_kernel(const float* logits, int count, int k, int win_h, int win_w, int top, int left, int H, int W,
+                                                                 const double* gains, uint16_t* labels) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int items_per_row = W / 4 + 2;
+    const int64_t items = (int64_t)count * H * items_per_row;
+    const size_t win_px = (size_t)win_h * win_w;
+    double g[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) g[c] = (gains && c < k) ? gains[c] : 0.0;
+    for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
+        const int64_t row = it / items_per_row;           // = s * H + y
+        const int i = (int)(it - row * items_per_row);
+        const int s = (int)(row / H), y = (int)(row - (int64_t)s * H);
+        const int head = min(W, (int)(((8 - (reinterpret_cast<uintptr_t>(labels + row * W) & 7)) & 7) >> 1));
+        const int xa = i == 0 ? 0 : head + 4 * (i - 1), xb = i == 0 ? head : min(W, xa + 4);
+        if (xa >= xb) continue;
+        const float* in = logits + (size_t)s * k * win_px + (size_t)(y - top) * win_w + (xa - left);
+        uint16_t* out = labels + row * W + xa;
+        if (k <= 8 && xb - xa == 4) {
+            float v[4][8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                if (c < k) {
+                    const f32x4a4 q = *reinterpret_cast<const f32x4a4*>(in + (size_t)c * win_px);
+                    v[0][c] = q[0]; v[1][c] = q[1]; v[2][c] = q[2]; v[3][c] = q[3];
+                }
+            u16x4a2 l;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint16_t label = ANH_LABEL_IGNORE;
+                float best = -INFINITY;
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+                    if (c < k) {
+                        const float value = (float)__dadd_rn((double)v[j][c], g[c]);
+                        if (value > best) { label = (uint16_t)c; best = value; }
+                    }
+                l[j] = label;
+            }
+            *reinterpret_cast<u16x4a2*>(out) = l;
+            continue;
+        }
+        for (int x = 0; x < xb - xa; ++x) {
+            uint16_t label = ANH_LABEL_IGNORE;
+            float best = -INFINITY;
+            for (int c = 0; c < k; ++c) {
+                const float value = (float)__dadd_rn((double)in[(size_t)c * win_px + x], gains ? gains[c] : 0.0);
+                if (value > best) { label = (uint16_t)c; best = value; }
+            }
+            out[x] = label;
+        }
     }
 }
 
@@ -2170,7 +2228,7 @@ bool blend_batch_ok(const BlendBatchArgs& a) {
     if (a.count > 16 || a.k < 1 || a.k > 4) return false;
     for (int i = 0; i < a.count; ++i)
         for (int j = 0; j < a.count; ++j)
-            if (j != i && a.unique[i][0] <= a.full[j][2] && a.full[j][0] <= a.unique[i][2] && a.unique[i][1] <= a.full[j][3] && a.full[j][1] <= a.unique[i][3]) return false;
+            if (j != i && a.image[j] == a.image[i] && a.unique[i][0] <= a.full[j][2] && a.full[j][0] <= a.unique[i][2] && a.unique[i][1] <= a.full[j][3] && a.full[j][1] <= a.unique[i][3]) return false;
     return true;
 }
 
@@ -2180,7 +2238,7 @@ void launch_blend_batch(BlendBatchArgs a, hipStream_t s) {
     for (int i = 0; i < a.count; ++i) {
         a.nbr[i] = 0;
         for (int j = 0; j < a.count; ++j)
-            if (j != i && a.full[i][0] <= a.full[j][2] && a.full[j][0] <= a.full[i][2] && a.full[i][1] <= a.full[j][3] && a.full[j][1] <= a.full[i][3]) a.nbr[i] |= 1u << j;
+            if (j != i && a.image[j] == a.image[i] && a.full[i][0] <= a.full[j][2] && a.full[j][0] <= a.full[i][2] && a.full[i][1] <= a.full[j][3] && a.full[j][1] <= a.full[i][3]) a.nbr[i] |= 1u << j;
     }
     hipLaunchKernelGGL(blend_batch_kernel, dim3((a.tile_w + 255) / 256, a.tile_h, a.count), dim3(256), 0, s, a);
     HIP_CHECK(hipGetLastError());
@@ -2201,6 +2259,18 @@ void launch_argmax_range(const float* blended, int k, int64_t pixels, int64_t p0
     const int64_t per = k <= 8 ? 1024 : 256;   // pixels per workgroup and pass
     const int blocks = (int)std::min<int64_t>((p1 - p0 + per - 1) / per, 256 * 16);
     hipLaunchKernelGGL(argmax_kernel, dim3(blocks), dim3(256), 0, s, blended, k, pixels, p0, p1, gains_or_null, labels);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_labels_from_logits(const float* logits, int count, int k, int win_h, int win_w, int top, int left, int height, int width,
+                               const double* gains_or_null, uint16_t* labels, hipStream_t s) {
+    if (count <= 0) return;
+    ANH_REQUIRE(k >= 1 && height >= 1 && width >= 1 && win_h >= 1 && win_w >= 1, "labels_from_logits: empty shape");
+    // every image pixel must lie inside the window: the kernel reads logits at (y - top, x - left) for all of [0, height) x [0, width)
+    ANH_REQUIRE(top <= 0 && left <= 0 && (int64_t)height - top <= win_h && (int64_t)width - left <= win_w, "labels_from_logits: the window does not cover the image");
+    const int64_t items = (int64_t)count * height * (width / 4 + 2);
+    const int blocks = (int)std::min<int64_t>((items + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(labels_from_logits_kernel, dim3(blocks), dim3(256), 0, s, logits, count, k, win_h, win_w, top, left, height, width, gains_or_null, labels);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -2461,7 +2461,7 @@ __global__ __launch_bounds__(256, (ACT ? 4 : 2)) void stem_mfma_kernel(ConvArgs 
     auto fetch = [&](int tile_) __attribute__((always_inline)) {
         const int tx = tile_ % tiles_x, ty = (tile_ / tiles_x) % tiles_y, n = tile_ / (tiles_x * tiles_y);
         const int x0 = tx * 32, y0 = ty * 8;
-        const uint8_t* img = a.src.img + (size_t)n * a.src.img_sample_stride;
+        const uint8_t* img = a.src.img + (size_t)a.src.image_of(n) * a.src.img_sample_stride;
         pvalid = 0;
 #pragma unroll
         for (int u = 0; u < NPX; ++u) {

@@ -8,7 +8,7 @@
 // excluding the first image: average = ... ms, max = ... ms", both confusion matrices), the files it reads (annonet.dnn,
 // <image>_mask.png) and writes (<image>_result.png), and its exit codes (2 for option errors, 1 otherwise).
 // Extensions: --precision fp32|bf16, --devices 0,1,... (tile lists sharded over several GPUs from this one process), --dnn <file>,
-// --host-resize.  A net with a downscaling factor other than 1: the image goes to the GPU at its original size and annonet_infer_scaled()
+// --host-resize, --image-batch N (consecutive images of one size go through annonet_infer_batch() together).  A net with a downscaling factor other than 1: the image goes to the GPU at its original size and annonet_infer_scaled()
 // shrinks it, infers and blows the label map back up there (the reference does both resizes on the CPU: annonet.cpp:153 in the readers,
 // annonet_infer_main.cpp:413 in the writers); --host-resize keeps them on this program's reader / writer threads.  Same files, same matrices.
 #define ANNONET_HIP_NO_DLIB
@@ -27,6 +27,7 @@ struct Settings {
     std::vector<int> devices;
     int max_tile_w = 1024, max_tile_h = 1024;   // the reference's GPU-build defaults (:300-303)
     bool host_resize = false;
+    int image_batch = 1;
     int readers = (int)std::max(1u, std::thread::hardware_concurrency()), writers = (int)std::max(1u, std::thread::hardware_concurrency());
 };
 
@@ -42,7 +43,11 @@ const char* usage_text() {
            "      --precision fp32|bf16            fp32 = bit-exact parity mode, bf16 = MFMA throughput mode (default)\n"
            "      --devices 0,1,...                GPUs this process drives (tile lists are sharded over them)\n"
            "      --dnn file                       trained net (default: annonet.dnn)\n"
-           "      --host-resize                    downscaled nets: resize image and label map on the CPU threads, not on the GPU\n";
+           "      --host-resize                    downscaled nets: resize image and label map on the CPU threads, not on the GPU\n"
+           "      --image-batch N                  up to N consecutive images of one size run as one batch (default: 1, image by image);\n"
+           "                                       taken when the net's downscaling factor is 1 or with --host-resize; with --devices the\n"
+           "                                       images of a batch are dealt out to the GPUs.  A batch's time is charged in equal parts\n"
+           "                                       to its images, and \"excluding the first image\" then excludes the first batch\n";
 }
 
 Settings read_command_line(int argc, char** argv) {
@@ -56,6 +61,7 @@ Settings read_command_line(int argc, char** argv) {
         {"--full-image-reader-thread-count", [&](const std::string& v) { s.readers = std::stoi(v); }},
         {"--result-image-writer-thread-count", [&](const std::string& v) { s.writers = std::stoi(v); }},
         {"--precision", [&](const std::string& v) { s.precision = v; }}, {"--dnn", [&](const std::string& v) { s.dnn_file = v; }},
+        {"--image-batch", [&](const std::string& v) { s.image_batch = std::stoi(v); }},
         {"--devices", [&](const std::string& v) { std::stringstream list(v); std::string item; while (std::getline(list, item, ',')) s.devices.push_back(std::stoi(item)); }},
     };
     for (int i = 1; i < argc; ++i) {
@@ -71,6 +77,7 @@ Settings read_command_line(int argc, char** argv) {
     }
     if (s.directory.empty()) throw std::runtime_error("Option 'input-directory' is required but not present");
     if (s.precision != "bf16" && s.precision != "fp32") throw std::runtime_error("--precision must be fp32 or bf16");
+    if (s.image_batch < 1) throw std::runtime_error("--image-batch must be at least 1");
     return s;
 }
 
@@ -200,10 +207,18 @@ struct InferenceClock {
         all += d;
         if (images++ > 0) { after_first += d; slowest_after_first = std::max(slowest_after_first, d); }   // the first image pays the warm-up
     }
+    // a batch of `count` images (--image-batch): its duration in equal parts to its images; the first BATCH pays the warm-up
+    void record_batch(us d, size_t count) {
+        all += d;
+        if (images > 0) { after_first += d; slowest_after_first = std::max(slowest_after_first, us(d.count() / (long long)count)); }
+        else first_batch_images = count;
+        images += count;
+    }
+    size_t first_batch_images = 1;
     void report(double wall_seconds) const {
         std::cout << "\nAll " << images << " images processed in " << wall_seconds << " seconds! (actual inference: " << all.count() / 1000000.0 << " seconds)" << std::endl;
-        if (images > 1)
-            std::cout << "Processing time excluding the first image: average = " << after_first.count() / 1000.0 / (images - 1) << " ms, max = " << slowest_after_first.count() / 1000.0
+        if (images > first_batch_images)
+            std::cout << "Processing time excluding the first image: average = " << after_first.count() / 1000.0 / (images - first_batch_images) << " ms, max = " << slowest_after_first.count() / 1000.0
                       << " ms" << std::endl;
     }
 };
@@ -233,27 +248,59 @@ int run(const Settings& settings) {
         ImageReaders readers(files, settings.readers, trained.classes, trained.downscaling, !resize_on_gpu);
         ResultWriters writers(settings.writers, files.size(), trained.classes);
         const auto started = std::chrono::steady_clock::now();
-        for (size_t i = 0; i < files.size(); ++i) {
-            std::cout << "\rProcessing image " << (i + 1) << " of " << files.size() << "...";
-            const sample_type sample = readers.next();
-            LabelMapToWrite result;
-            result.path = sample.image_filenames.image_filename + "_result.png";
-            result.width = sample.original_width; result.height = sample.original_height;
-
-            const auto t0 = std::chrono::steady_clock::now();
-            if (resize_on_gpu) annonet_infer_scaled(trained.net, sample.input_image, trained.downscaling, result.labels, scratch, gains, detection_levels, tiles);
-            else annonet_infer(trained.net, sample.input_image, result.labels, scratch, gains, detection_levels, tiles);
-            clock.record(std::chrono::duration_cast<InferenceClock::us>(std::chrono::steady_clock::now() - t0));
-            // both matrices are scored at the net's resolution (the ground truth was resized to it, annonet.cpp:160-166)
-            const dlib::matrix<uint16_t>& scored = resize_on_gpu ? scratch.scaled_result_image : result.labels;
-
+        // both matrices are scored at the net's resolution (the ground truth was resized to it, annonet.cpp:160-166)
+        auto score = [&](const sample_type& sample, const dlib::matrix<uint16_t>& scored) {
             for (const auto& cls_points : sample.labeled_points_by_class) {   // per-pixel score on the annotated pixels (:482-490)
                 for (const dlib::point& p : cls_points.second) per_pixel.add(cls_points.first, scored(p.y(), p.x()));
                 labelled_pixels += cls_points.second.size();
             }
             region_scorer.score(per_region, sample, scored);
+        };
+        auto result_for = [](const sample_type& sample) {
+            LabelMapToWrite result;
+            result.path = sample.image_filenames.image_filename + "_result.png";
+            result.width = sample.original_width; result.height = sample.original_height;
+            return result;
+        };
+        // --image-batch N > 1: up to N consecutive samples of one size wait here and go through annonet_infer_batch() together; a sample
+        // of another size flushes them first.  (The images reach the GPU at the net's resolution on this path: factor 1, or --host-resize.)
+        const bool batched = settings.image_batch > 1 && !resize_on_gpu;
+        std::vector<sample_type> pending;
+        auto flush = [&] {
+            if (pending.empty()) return;
+            std::vector<NetPimpl::input_type> images;
+            for (sample_type& s : pending) images.push_back(std::move(s.input_image));
+            std::vector<dlib::matrix<uint16_t>> maps;
+            const auto t0 = std::chrono::steady_clock::now();
+            annonet_infer_batch(trained.net, images, maps, scratch, gains, detection_levels, tiles);
+            clock.record_batch(std::chrono::duration_cast<InferenceClock::us>(std::chrono::steady_clock::now() - t0), pending.size());
+            for (size_t j = 0; j < pending.size(); ++j) {
+                LabelMapToWrite result = result_for(pending[j]);
+                result.labels = std::move(maps[j]);
+                score(pending[j], result.labels);
+                writers.submit(std::move(result));
+            }
+            pending.clear();
+        };
+        for (size_t i = 0; i < files.size(); ++i) {
+            std::cout << "\rProcessing image " << (i + 1) << " of " << files.size() << "...";
+            sample_type sample = readers.next();
+            if (batched) {
+                if (!pending.empty() && (sample.input_image.nr() != pending[0].input_image.nr() || sample.input_image.nc() != pending[0].input_image.nc())) flush();
+                pending.push_back(std::move(sample));
+                if ((int)pending.size() == settings.image_batch) flush();
+                continue;
+            }
+            LabelMapToWrite result = result_for(sample);
+
+            const auto t0 = std::chrono::steady_clock::now();
+            if (resize_on_gpu) annonet_infer_scaled(trained.net, sample.input_image, trained.downscaling, result.labels, scratch, gains, detection_levels, tiles);
+            else annonet_infer(trained.net, sample.input_image, result.labels, scratch, gains, detection_levels, tiles);
+            clock.record(std::chrono::duration_cast<InferenceClock::us>(std::chrono::steady_clock::now() - t0));
+            score(sample, resize_on_gpu ? scratch.scaled_result_image : result.labels);
             writers.submit(std::move(result));
         }
+        flush();
         clock.report(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - started).count() / 1000.0);
         writers.wait_for_all();
         std::cout << "All result images written!" << std::endl;

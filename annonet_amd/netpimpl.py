@@ -366,6 +366,68 @@ def annonet_infer_device(net, d_image_ptr, height, width, d_labels_ptr, d_blende
     check(net.L.anh_infer_device(net.h, d_image_ptr, height, width, _ptr(g), C.byref(tp) if tp is not None else None, arr, n, d_labels_ptr, d_blended_ptr))
 
 
+def annonet_infer_batch(net, input_images, gains=None, detection_levels=None, tiling_parameters=None, want_blended=False):
+    """annonet_infer() over several images of ONE size in one call (anh_infer_batch): a list of u8 images (or an array [n,H,W,C]) ->
+    list of u16 label images (and, with want_blended, the list of their blended class planes).  want_blended may also be a list of
+    booleans, one per image.  Every image's result equals annonet_infer() of that image alone, bit for bit."""
+    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in input_images]
+    imgs = [im[:, :, None] if im.ndim == 2 else im for im in imgs]
+    n = len(imgs)
+    K = net.cfg.classes
+    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
+    d = np.ascontiguousarray(detection_levels, dtype=np.float64) if detection_levels is not None else None
+    if g is not None and g.size != K or d is not None and d.size != K:
+        raise AnnonetHipError(1, "gains / detection levels need one value per class")
+    if n and any(im.shape != imgs[0].shape for im in imgs):
+        raise AnnonetHipError(1, "the images of a batch must have one size and channel count")
+    if n and imgs[0].shape[2] != net.cfg.in_channels:
+        raise AnnonetHipError(1, "channel count does not match the net input")
+    H, W = imgs[0].shape[:2] if n else (0, 0)
+    want = list(want_blended) if isinstance(want_blended, (list, tuple)) else [bool(want_blended)] * n
+    res = [np.empty((H, W), np.uint16) for _ in range(n)]
+    bl = [np.empty((K, H, W), np.float32) if w else None for w in want]
+    ptrs = lambda arrays: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a is not None else None for a in arrays])
+    tp = tiling_parameters._c() if tiling_parameters is not None else None
+    check(net.L.anh_infer_batch(net.h, ptrs(imgs), n, H, W, _ptr(g), _ptr(d), C.byref(tp) if tp is not None else None, ptrs(res),
+                                ptrs(bl) if any(want) else None))
+    return (res, bl) if any(want) or want_blended else res
+
+
+def annonet_infer_batch_device(net, d_images_ptr, n, height, width, d_labels_ptr, d_blended_ptr=0, gains=None, tiling_parameters=None):
+    """annonet_infer_batch with the images [n,H,W,C], the label maps [n,H,W] and (optionally) the planes [n,K,H,W] resident in HBM
+    (device pointers as ints); enqueued on the handle's stream, not synchronised."""
+    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
+    tp = tiling_parameters._c() if tiling_parameters is not None else None
+    check(net.L.anh_infer_batch_device(net.h, d_images_ptr, n, height, width, _ptr(g), C.byref(tp) if tp is not None else None, d_labels_ptr, d_blended_ptr or None))
+
+
+def labels_from_logits_device(net, d_logits_ptr, count, classes, win_height, win_width, top, left, height, width, d_labels_ptr, gains=None):
+    """find_label straight from the logits [count,classes,win_height,win_width] of whole-image tiles whose window starts at (left, top):
+    label maps [count,height,width] (anh_labels_from_logits_device)."""
+    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
+    check(net.L.anh_labels_from_logits_device(net.h, d_logits_ptr, count, classes, win_height, win_width, top, left, height, width, _ptr(g), d_labels_ptr))
+
+
+def infer_batch_plan(tiles, n_images, levels, cap):
+    """anh_infer_batch_plan: tiles = one image's list of (full, unique) rectangles -> the forward batches, each a list of (image, tile)."""
+    arr = (_lib.Tile * max(len(tiles), 1))()
+    for i, (full, uniq) in enumerate(tiles):
+        arr[i].full_rect = _lib.Rect(*full)
+        arr[i].unique_rect = _lib.Rect(*uniq)
+    pairs, sizes, nb = C.POINTER(C.c_int)(), C.POINTER(C.c_int)(), C.c_size_t()
+    L = _lib.lib()
+    check(L.anh_infer_batch_plan(arr, len(tiles), n_images, levels, cap, C.byref(pairs), C.byref(sizes), C.byref(nb)))
+    try:
+        out, k = [], 0
+        for b in range(nb.value):
+            out.append([(pairs[2 * (k + j)], pairs[2 * (k + j) + 1]) for j in range(sizes[b])])
+            k += sizes[b]
+        return out
+    finally:
+        L.anh_free(pairs)
+        L.anh_free(sizes)
+
+
 def scaled_dims(height, width, downscaling_factor):
     """anh_scaled_dims: (scaled height, scaled width) = the size dlib::resize_image(1.0 / factor, img) gives (annonet.cpp:153)."""
     sh, sw = C.c_int(), C.c_int()

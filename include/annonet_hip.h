@@ -156,6 +156,30 @@ int anh_infer(anh_runtime* h, const uint8_t* image_hwc, int height, int width,
 int anh_infer_device(anh_runtime* h, const uint8_t* d_image_hwc, int height, int width,
                      const double* gains, const anh_tiling_params* tiling,
                      const anh_tile* tiles, size_t n_tiles, uint16_t* d_result_labels, float* d_blended);
+/* annonet_infer() over n >= 1 images of ONE size in one call (a folder of camera frames): the images' tile lists are concatenated image by
+ * image and cut into forward batches that may span image boundaries, so frames that are one tile each run the net with several frames
+ * per launch.  Every image's label map (and planes) equal, bit for bit, what anh_infer returns for that image alone.
+ * images_hwc / results: n host pointers; blended_out: NULL, or n pointers of which each may be NULL.  Where every image is one tile and
+ * neither planes nor detection levels are asked for, the labels come straight from the batch's logits and no planes are written.
+ * A batch that does not fit returns ANH_ERR_OOM before any kernel is enqueued and leaves the handle usable.  On a handle with R replicas
+ * replica r computes the images anh_shard_range(n, R, r) (an image is computed wholly on one replica); n < R goes image by image. */
+int anh_infer_batch(anh_runtime* h, const uint8_t* const* images_hwc, int n, int height, int width,
+                    const double* gains, const double* detection_levels, const anh_tiling_params* tiling,
+                    uint16_t* const* results, float* const* blended_out);
+/* the same with everything resident in HBM on the handle's first device, enqueued on the handle's stream without synchronising:
+ * d_images_hwc [n][H][W][C], d_results [n][H][W], d_blended [n][K][H][W] or NULL */
+int anh_infer_batch_device(anh_runtime* h, const uint8_t* d_images_hwc, int n, int height, int width,
+                           const double* gains, const anh_tiling_params* tiling, uint16_t* d_results, float* d_blended);
+/* find_label (annonet_infer.cpp:170-185) straight from the logits of a batch whose samples are whole images: d_logits
+ * [count][classes][win_height][win_width] fp32, the net input window starting at (left, top) in image coordinates and covering the image
+ * (top <= 0, left <= 0, height - top <= win_height, width - left <= win_width); d_result [count][height][width].  gains: `classes`
+ * host doubles or NULL.  With the window equal to the image it labels `count` sets of class planes in one launch. */
+int anh_labels_from_logits_device(anh_runtime* h, const float* d_logits, int count, int classes, int win_height, int win_width, int top, int left,
+                                  int height, int width, const double* gains, uint16_t* d_result);
+/* the host logic of the batches, exported for tests: the tile list of ONE image, n_images images, the net's level count and a cap on the
+ * batch size -> *pairs = (image, tile) index pairs in forward order (2 * n_tiles * n_images ints), *batch_sizes = the size of each of the
+ * *n_batches batches; both blocks are released with anh_free */
+int anh_infer_batch_plan(const anh_tile* tiles, size_t n_tiles, int n_images, int levels, int cap, int** pairs, int** batch_sizes, size_t* n_batches);
 /* ---- downscaled inference: a net trained with a downscaling factor (annonet.dnn carries it) sees every image shrunk by it ----
  * read_sample shrinks the image with dlib::resize_image(1.0 / factor, image), bilinear (annonet.cpp:153); the inference program blows the
  * label map back up with resize_label_image, nearest neighbour (annonet_infer_main.cpp:413, annonet.cpp:132-141).  Both run on the device

@@ -56,6 +56,45 @@ inline void annonet_infer(NetPimpl::RuntimeNet& net, const NetPimpl::input_type&
     }
 }
 
+// annonet_infer() over several images of ONE size in one call (anh_infer_batch): a folder of camera frames that are one tile each runs the
+// net with several frames per launch, and every result equals annonet_infer() of that image alone, bit for bit.  result_images[i]
+// belongs to input_images[i].  temp.blended_output keeps its keep_blended_output rule and holds the planes of the LAST image, as it
+// would after a loop of annonet_infer() calls.
+inline void annonet_infer_batch(NetPimpl::RuntimeNet& net, const std::vector<NetPimpl::input_type>& input_images, std::vector<dlib::matrix<uint16_t>>& result_images,
+                                annonet_infer_temp& temp, const std::vector<double>& gains = std::vector<double>(),
+                                const std::vector<double>& detection_levels = std::vector<double>(),
+                                const tiling::parameters& tiling_parameters = tiling::parameters()) {
+    anh_net_config cfg;
+    NetPimpl::check(anh_runtime_config(net.handle(), &cfg));
+    if (input_images.empty()) throw std::runtime_error("annonet_infer_batch: the batch needs at least one image");
+    const int K = cfg.classes, n = (int)input_images.size(), H = (int)input_images[0].nr(), W = (int)input_images[0].nc();
+    if (!gains.empty() && (int)gains.size() != K) throw std::runtime_error("annonet_infer_batch: one gain per class expected");
+    if (!detection_levels.empty() && (int)detection_levels.size() != K) throw std::runtime_error("annonet_infer_batch: one detection level per class expected");
+    std::vector<const uint8_t*> images((size_t)n);
+    std::vector<uint16_t*> results((size_t)n);
+    std::vector<float*> planes_of((size_t)n, nullptr);
+    result_images.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if ((int)input_images[i].nr() != H || (int)input_images[i].nc() != W) throw std::runtime_error("annonet_infer_batch: the images of a batch must have one size");
+        images[i] = reinterpret_cast<const uint8_t*>(&*input_images[i].begin());
+        result_images[i].set_size(H, W);
+        results[i] = &*result_images[i].begin();
+    }
+    std::vector<float> planes;
+    if (temp.keep_blended_output) { planes.resize((size_t)K * H * W); planes_of[n - 1] = planes.data(); }
+    anh_tiling_params tp{tiling_parameters.max_tile_width, tiling_parameters.max_tile_height, tiling_parameters.overlap_x, tiling_parameters.overlap_y};
+    NetPimpl::check(anh_infer_batch(net.handle(), images.data(), n, H, W, gains.empty() ? nullptr : gains.data(),
+                                    detection_levels.empty() ? nullptr : detection_levels.data(), &tp, results.data(),
+                                    temp.keep_blended_output ? planes_of.data() : nullptr));
+    if (temp.keep_blended_output) {
+        temp.blended_output.resize(K);
+        for (int k = 0; k < K; ++k) {
+            temp.blended_output[k].set_size(H, W);
+            std::copy(planes.begin() + (size_t)k * H * W, planes.begin() + (size_t)(k + 1) * H * W, temp.blended_output[k].begin());
+        }
+    }
+}
+
 // What the reference's inference program does around annonet_infer() for a net trained with a downscaling factor, in one call on the
 // GPU: read_sample's dlib::resize_image(1.0 / factor, image) (annonet.cpp:153, bilinear), annonet_infer() on the shrunk image
 // (annonet_infer_main.cpp:468) and resize_label_image back to the original size (annonet_infer_main.cpp:413, annonet.cpp:132-141, nearest
