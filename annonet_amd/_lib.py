@@ -145,6 +145,10 @@ _SIGNATURES = {  # ConvDesc / OpInput are defined above
     "anh_resize_labels_device": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
     "anh_infer_scaled": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, _P, _P, C.POINTER(TilingParams), _P, _P, _P]),
     "anh_infer_scaled_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, _P, C.POINTER(TilingParams), _P, _P, _P]),
+    "anh_resize_image_batch_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "anh_resize_labels_batch_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "anh_infer_scaled_batch": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, C.POINTER(TilingParams), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "anh_infer_scaled_batch_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.POINTER(TilingParams), _P, _P, _P]),
     "anh_runtime_set_stream": (C.c_int, [_P, _P]),
     "anh_runtime_get_stream": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "anh_runtime_synchronize": (C.c_int, [_P]),

@@ -921,6 +921,119 @@ int anh_infer_scaled(anh_runtime* h, const uint8_t* image, int height, int width
     });
 }
 
+// ---- downscaled inference over n images of one original size: anh_infer_scaled composed with anh_infer_batch ----
+int anh_resize_image_batch_device(const uint8_t* d_src, int count, int channels, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w, void* hip_stream) {
+    return guarded([&] {
+        ANH_REQUIRE(count >= 1, "resize_image: the batch needs at least one image");
+        ANH_REQUIRE(d_src && d_dst, "null argument");
+        ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1 && src_h <= 32768 && src_w <= 32768 && dst_h <= 32768 && dst_w <= 32768, "resize_image: sides must be within 1..32768");
+        launch_resize_image_bilinear_batch(d_src, count, channels, src_h, src_w, d_dst, dst_h, dst_w, (hipStream_t)hip_stream);
+    });
+}
+
+int anh_resize_labels_batch_device(const uint16_t* d_src, int count, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w, void* hip_stream) {
+    return guarded([&] {
+        ANH_REQUIRE(count >= 1, "resize_labels: the batch needs at least one label image");
+        ANH_REQUIRE(d_src && d_dst, "null argument");
+        ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1 && src_h <= 32768 && src_w <= 32768 && dst_h <= 32768 && dst_w <= 32768, "resize_labels: sides must be within 1..32768");
+        launch_resize_labels_nearest_batch(d_src, count, src_h, src_w, d_dst, dst_h, dst_w, (hipStream_t)hip_stream);
+    });
+}
+
+int anh_infer_scaled_batch_device(anh_runtime* h, const uint8_t* d_images, int n, int height, int width, double downscaling_factor, const double* gains,
+                                  const anh_tiling_params* tiling, uint16_t* d_results, uint16_t* d_scaled_labels, float* d_blended) {
+    return guarded([&] {
+        ANH_REQUIRE(n >= 1, "infer_batch: the batch needs at least one image");
+        ANH_REQUIRE(h && d_images && d_results, "null argument");
+        int sh = 0, sw = 0;
+        scaled_dims_checked(height, width, downscaling_factor, sh, sw);
+        DeviceScope scope(h->reps.device_of(0));
+        Engine& e = h->reps.engine(0);
+        const int C = e.spec.cfg.in_channels;
+        const size_t plane = (size_t)sh * sw;
+        const std::vector<anh_tile> tiles = tiles_for(tiling, sw, sh);
+        if (downscaling_factor == 1.0) {   // as anh_infer_scaled_device: no resize at scale 1
+            e.infer_batch_device(d_images, n, height, width, gains, tiles, d_results, d_blended);
+            if (d_scaled_labels) HIP_CHECK(hipMemcpyAsync(d_scaled_labels, d_results, (size_t)n * plane * 2, hipMemcpyDeviceToDevice, e.stream));
+            return;
+        }
+        // reserved before the first kernel; infer_batch_device reserves its own (planes, logits) before its first kernel and writes nothing
+        // the shrink does not own, so a batch that cannot fit has only shrunk images into a stage buffer
+        e.stage_image.reserve((size_t)n * plane * C);
+        if (!d_scaled_labels) { e.stage_result.reserve((size_t)n * plane * 2); d_scaled_labels = e.stage_result.as<uint16_t>(); }
+        e.reserve_infer_batch(n, sh, sw, tiles, d_blended != nullptr);
+        e.resize_image_batch(d_images, n, height, width, e.stage_image.as<uint8_t>(), sh, sw);
+        e.infer_batch_device(e.stage_image.as<uint8_t>(), n, sh, sw, gains, tiles, d_scaled_labels, d_blended);
+        e.resize_labels_batch(d_scaled_labels, n, sh, sw, d_results, height, width);
+    });
+}
+
+int anh_infer_scaled_batch(anh_runtime* h, const uint8_t* const* images, int n, int height, int width, double downscaling_factor, const double* gains,
+                           const double* detection_levels, const anh_tiling_params* tiling, uint16_t* const* results, uint16_t* const* scaled_labels,
+                           float* const* blended_out) {
+    return guarded([&] {
+        ANH_REQUIRE(n >= 1, "infer_batch: the batch needs at least one image");
+        ANH_REQUIRE(images && results, "infer_batch: null image or result list");
+        ANH_REQUIRE(h, "null handle");
+        ANH_REQUIRE(height >= 1 && width >= 1, "empty image");
+        int sh = 0, sw = 0;
+        scaled_dims_checked(height, width, downscaling_factor, sh, sw);
+        for (int i = 0; i < n; ++i) ANH_REQUIRE(images[i] && results[i], "infer_batch: null image or result");
+        const size_t plane = (size_t)sh * sw, full = (size_t)height * width;
+        if (downscaling_factor == 1.0) {   // exactly anh_infer_batch, as anh_infer_scaled is exactly anh_infer
+            const int rc = anh_infer_batch(h, images, n, height, width, gains, detection_levels, tiling, results, blended_out);
+            if (rc != ANH_OK) fail(rc, g_error);
+            if (scaled_labels) for (int i = 0; i < n; ++i) if (scaled_labels[i]) std::memcpy(scaled_labels[i], results[i], full * 2);
+            return;
+        }
+        const size_t R = h->reps.size();
+        if ((size_t)n < R) {   // fewer images than replicas: image by image, as anh_infer_scaled serves them
+            for (int i = 0; i < n; ++i) {
+                const int rc = anh_infer_scaled(h, images[i], height, width, downscaling_factor, gains, detection_levels, tiling, results[i],
+                                                scaled_labels ? scaled_labels[i] : nullptr, blended_out ? blended_out[i] : nullptr);
+                if (rc != ANH_OK) fail(rc, g_error);
+            }
+            return;
+        }
+        const int K = h->reps.engine(0).spec.cfg.classes, C = h->reps.engine(0).spec.cfg.in_channels;
+        const std::vector<anh_tile> tiles = tiles_for(tiling, sw, sh);
+        const bool use_det = detection_requested(detection_levels, K);
+        // every replica takes a contiguous share of the images and shrinks, infers and blows up its own: nothing is exchanged
+        h->reps.each([&](size_t r, Engine& e) {
+            int64_t lo = 0, hi = 0;
+            shard_range((int64_t)n, (int)R, (int)r, lo, hi);
+            const int m = (int)(hi - lo);
+            if (m <= 0) return;
+            bool planes = use_det;   // the filter reads the planes
+            if (blended_out) for (int64_t i = lo; i < hi; ++i) planes = planes || blended_out[i] != nullptr;
+            e.stage_original.reserve((size_t)m * full * C);
+            e.stage_image.reserve((size_t)m * plane * C);
+            e.stage_result.reserve((size_t)m * plane * 2);
+            e.stage_upsampled.reserve((size_t)m * full * 2);
+            if (planes) e.stage_blended.reserve((size_t)m * plane * K * 4);
+            if (use_det) e.stage_out.reserve(detection_scratch_bytes(plane, K));
+            e.reserve_infer_batch(m, sh, sw, tiles, planes);
+            for (int i = 0; i < m; ++i)
+                HIP_CHECK(hipMemcpyAsync(e.stage_original.as<uint8_t>() + (size_t)i * full * C, images[lo + i], full * C, hipMemcpyHostToDevice, e.stream));
+            float* d_planes = planes ? e.stage_blended.as<float>() : nullptr;
+            uint16_t* d_labels = e.stage_result.as<uint16_t>();
+            uint16_t* d_up = e.stage_upsampled.as<uint16_t>();
+            e.resize_image_batch(e.stage_original.as<uint8_t>(), m, height, width, e.stage_image.as<uint8_t>(), sh, sw);
+            e.infer_batch_device(e.stage_image.as<uint8_t>(), m, sh, sw, gains, tiles, d_labels, d_planes);
+            if (use_det) for (int i = 0; i < m; ++i) apply_detection_levels(e, detection_levels, K, sh, sw, d_planes + (size_t)i * K * plane, d_labels + (size_t)i * plane);
+            e.resize_labels_batch(d_labels, m, sh, sw, d_up, height, width);
+            for (int i = 0; i < m; ++i) {
+                HIP_CHECK(hipMemcpyAsync(results[lo + i], d_up + (size_t)i * full, full * 2, hipMemcpyDeviceToHost, e.stream));
+                if (scaled_labels && scaled_labels[lo + i])
+                    HIP_CHECK(hipMemcpyAsync(scaled_labels[lo + i], d_labels + (size_t)i * plane, plane * 2, hipMemcpyDeviceToHost, e.stream));
+                if (blended_out && blended_out[lo + i])
+                    HIP_CHECK(hipMemcpyAsync(blended_out[lo + i], d_planes + (size_t)i * K * plane, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
+            }
+            e.synchronize();
+        });
+    });
+}
+
 int anh_runtime_set_stream(anh_runtime* h, void* s) { return guarded([&] { ANH_REQUIRE(h, "null handle"); ANH_REQUIRE(h->reps.size() == 1, "a handle that drives several devices keeps its own streams"); h->reps.engine(0).set_stream((hipStream_t)s); }); }
 int anh_runtime_get_stream(anh_runtime* h, void** s) { return guarded([&] { ANH_REQUIRE(h && s, "null argument"); *s = (void*)h->reps.engine(0).stream; }); }
 int anh_runtime_stores_activations(anh_runtime* h, int* yes) { return guarded([&] { ANH_REQUIRE(h && yes, "null argument"); *yes = h->reps.engine(0).infer_post ? 1 : 0; }); }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "hostlogic.h"
 #include "kernels.h"
 #include "spec.h"
 
@@ -132,6 +133,9 @@ class Engine {
     // planes of the engine's own are used where the labels cannot come straight from the logits).  `tiles` is the complete tiling of one image.
     void infer_batch_device(const uint8_t* d_images, int n, int H, int W, const double* gains_host, const std::vector<anh_tile>& tiles,
                             uint16_t* d_labels, float* d_blended);
+    // the reservations of infer_batch_device, on their own (nothing is enqueued); true = the labels come straight from the logits
+    bool reserve_infer_batch(const std::vector<std::vector<TileSample>>& plan, int n, int H, int W, const std::vector<anh_tile>& tiles, bool planes_given);
+    bool reserve_infer_batch(int n, int H, int W, const std::vector<anh_tile>& tiles, bool planes_given);
     void labels_from_logits(const float* d_logits, int count, int k, int win_h, int win_w, int top, int left, int H, int W, const double* d_gains, uint16_t* d_labels);
     DevBuf batch_planes;
     bool infer_post = false;   // this inference pass stores post-activation tensors (choose_inference_form)
@@ -164,6 +168,9 @@ class Engine {
     // [sh][sw][C] -> tiles -> d_scaled_labels [sh][sw] (and d_blended [K][sh][sw]) -> d_labels [H][W]
     void resize_image(const uint8_t* d_src, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w);
     void resize_labels(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w);
+    // ... over `count` images of one size, back to back, by one launch each
+    void resize_image_batch(const uint8_t* d_src, int count, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w);
+    void resize_labels_batch(const uint16_t* d_src, int count, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w);
     std::vector<float> host_out;
 
   private:

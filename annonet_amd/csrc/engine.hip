@@ -1153,6 +1153,26 @@ bool Engine::batch_logits_in_memory(int count, int h, int w) {
     return in_memory;
 }
 
+// What infer_batch_device reserves for a plan: the layer tensors and logits of every batch shape and, where the labels cannot come
+// straight from the logits (returns false) and the caller gives no planes, planes of the engine's own.  Enqueues nothing, so a caller
+// with work of its own in front of the forward (the batched shrink) can fail with ANH_ERR_OOM before that work starts.
+bool Engine::reserve_infer_batch(const std::vector<std::vector<TileSample>>& plan, int n, int H, int W, const std::vector<anh_tile>& tiles, bool planes_given) {
+    bool direct = tiles.size() == 1 && !planes_given;   // labels straight from the logits: single-tile images, no planes asked for
+    int last_count = 0, last_h = 0, last_w = 0;
+    for (const std::vector<TileSample>& b : plan) {
+        const TileWindow w = tile_window(tiles[(size_t)b[0].tile], spec.cfg.levels);
+        if ((int)b.size() == last_count && w.height == last_h && w.width == last_w) continue;
+        last_count = (int)b.size(); last_h = w.height; last_w = w.width;
+        if (!batch_logits_in_memory(last_count, last_h, last_w)) direct = false;
+    }
+    if (!direct && !planes_given) batch_planes.reserve((size_t)n * spec.cfg.classes * H * W * 4);
+    return direct;
+}
+bool Engine::reserve_infer_batch(int n, int H, int W, const std::vector<anh_tile>& tiles, bool planes_given) {
+    ANH_REQUIRE(n >= 1 && H >= 1 && W >= 1 && !tiles.empty(), "empty batch");
+    return reserve_infer_batch(infer_batch_plan(tiles, n, spec.cfg.levels, [this](int h, int w) { return tile_batch(h, w); }), n, H, W, tiles, planes_given);
+}
+
 // annonet_infer() over n images of one size in one call: the images' tile lists are concatenated and cut into forward batches that may
 // span image boundaries (infer_batch_plan), so a folder of frames that are one tile each runs the net with up to kMaxTileBatch frames per
 // launch.  Within an image the blends arrive in list order, as in infer_device: every image's planes and labels are those of the image alone.
@@ -1165,15 +1185,8 @@ void Engine::infer_batch_device(const uint8_t* d_images, int n, int H, int W, co
     prof.start_image();
     const std::vector<std::vector<TileSample>> plan = infer_batch_plan(tiles, n, spec.cfg.levels, [this](int h, int w) { return tile_batch(h, w); });
     // Everything the call needs is reserved before its first kernel is enqueued: a batch that cannot fit fails here with ANH_ERR_OOM.
-    bool direct = tiles.size() == 1 && !d_blended;   // labels straight from the logits: single-tile images, no planes asked for
-    int last_count = 0, last_h = 0, last_w = 0;
-    for (const std::vector<TileSample>& b : plan) {
-        const TileWindow w = tile_window(tiles[(size_t)b[0].tile], spec.cfg.levels);
-        if ((int)b.size() == last_count && w.height == last_h && w.width == last_w) continue;
-        last_count = (int)b.size(); last_h = w.height; last_w = w.width;
-        if (!batch_logits_in_memory(last_count, last_h, last_w)) direct = false;
-    }
-    if (!direct && !d_blended) { batch_planes.reserve((size_t)n * K * pixels * 4); d_blended = batch_planes.as<float>(); }
+    const bool direct = reserve_infer_batch(plan, n, H, W, tiles, d_blended != nullptr);
+    if (!direct && !d_blended) d_blended = batch_planes.as<float>();
     const double* d_gains = upload_gains(gains_host);
     if (!direct && tiles.size() > 1) {   // only the frames are accumulated into (infer_device); a single tile assigns every pixel
         prepare_zero_rects(H, W, tiles);
@@ -1199,16 +1212,19 @@ void Engine::argmax_rows(const float* d_blended, int H, int W, int row0, int row
     prof.end(stream, tok);
 }
 
-void Engine::resize_image(const uint8_t* d_src, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w) {
+void Engine::resize_image(const uint8_t* d_src, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w) { resize_image_batch(d_src, 1, src_h, src_w, d_dst, dst_h, dst_w); }
+void Engine::resize_labels(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w) { resize_labels_batch(d_src, 1, src_h, src_w, d_dst, dst_h, dst_w); }
+
+void Engine::resize_image_batch(const uint8_t* d_src, int count, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w) {
     const int C = spec.cfg.in_channels;
-    const int tok = prof.begin(stream, "resize_image_bilinear", 0, ((double)src_h * src_w + (double)dst_h * dst_w) * C);
-    launch_resize_image_bilinear(d_src, C, src_h, src_w, d_dst, dst_h, dst_w, stream);
+    const int tok = prof.begin(stream, "resize_image_bilinear", 0, (double)count * ((double)src_h * src_w + (double)dst_h * dst_w) * C);
+    launch_resize_image_bilinear_batch(d_src, count, C, src_h, src_w, d_dst, dst_h, dst_w, stream);
     prof.end(stream, tok);
 }
 
-void Engine::resize_labels(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w) {
-    const int tok = prof.begin(stream, "resize_labels_nearest", 0, ((double)src_h * src_w + (double)dst_h * dst_w) * 2.0);
-    launch_resize_labels_nearest(d_src, src_h, src_w, d_dst, dst_h, dst_w, stream);
+void Engine::resize_labels_batch(const uint16_t* d_src, int count, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w) {
+    const int tok = prof.begin(stream, "resize_labels_nearest", 0, (double)count * ((double)src_h * src_w + (double)dst_h * dst_w) * 2.0);
+    launch_resize_labels_nearest_batch(d_src, count, src_h, src_w, d_dst, dst_h, dst_w, stream);
     prof.end(stream, tok);
 }
 

@@ -265,6 +265,10 @@ void launch_zero_rects(float* planes, int k, int H, int W, const anh_rect* d_rec
 // Any source and destination size; every destination element is written.
 void launch_resize_image_bilinear(const uint8_t* d_src, int channels, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w, hipStream_t s);
 void launch_resize_labels_nearest(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w, hipStream_t s);
+// ... over `count` images of one size that lie back to back ([count][h][w][C], [count][h][w]) by one launch: the kernels of the calls
+// above, which are their count = 1 case.  Every image is resized on its own, with the scales of the single-image call.
+void launch_resize_image_bilinear_batch(const uint8_t* d_src, int count, int channels, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w, hipStream_t s);
+void launch_resize_labels_nearest_batch(const uint16_t* d_src, int count, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w, hipStream_t s);
 
 // Training crops cut on the device from full images resident in HBM (randomly_crop_image, annonet_train_main.cpp:110-232,
 // for further_downscaling_factor = 1 and given draws).  kCropMaxClasses bounds the label values the histogram covers.

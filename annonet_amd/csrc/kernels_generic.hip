@@ -2418,16 +2418,23 @@ void launch_fill_zero(void* p, size_t bytes, hipStream_t s) {
 // coordinates in double, the fractions and the interpolation in float, rounded half up.  The arithmetic is the host's expression tree
 // evaluated operation by operation: it is bit-exact only because the build compiles with -ffp-contract=off (no fused multiply-add).
 //
-// A work item is (output row, chunk of 256 units); a unit is what one lane writes: kResizeImagePixels consecutive output pixels
+// A work item is (image, output row, chunk of 256 units); a unit is what one lane writes: kResizeImagePixels consecutive output pixels
 // (4 or 12 bytes) that start on a dword boundary of the destination, so a full unit leaves as 1 or 3 dword stores.  Rows start at any
-// byte address (width * channels is arbitrary): the first `head` pixels of a row (0..3) and the last few go out as bytes.
+// byte address (width * channels is arbitrary, and so is an image's start within a batch): the first `head` pixels of a row (0..3) and
+// the last few go out as bytes.  The `count` images of a batch lie back to back, [count][rows][cols][C], and are resized each on its
+// own: no row or column of one image reads another, and all share x_scale / y_scale.  One image is the batch of one.
 constexpr int kResizeImagePixels = 4;
 template <int C>
-__global__ __launch_bounds__(256) void resize_image_bilinear_kernel(const uint8_t* __restrict__ src, int in_nr, int in_nc, uint8_t* __restrict__ dst, int out_nr, int out_nc,
+__global__ __launch_bounds__(256) void resize_image_bilinear_kernel(const uint8_t* __restrict__ src_all, int in_nr, int in_nc, uint8_t* __restrict__ dst_all, int out_nr, int out_nc,
                                                                      int chunks, int64_t items) {
     const double x_scale = (in_nc - 1) / (double)max(out_nc - 1, 1), y_scale = (in_nr - 1) / (double)max(out_nr - 1, 1);
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int r = (int)(item / chunks), chunk = (int)(item - (int64_t)r * chunks);
+        const int64_t row = item / chunks;   // row of the whole batch
+        const int chunk = (int)(item - row * chunks);
+        const int64_t img = row / out_nr;
+        const int r = (int)(row - img * out_nr);
+        const uint8_t* src = src_all + img * in_nr * in_nc * C;
+        uint8_t* dst = dst_all + img * out_nr * out_nc * C;
         // per-row quantities, once per work item
         const double y = r * y_scale;
         const int top = min(max((int)floor(y), 0), in_nr - 1), bottom = min(top + 1, in_nr - 1);
@@ -2466,33 +2473,43 @@ __global__ __launch_bounds__(256) void resize_image_bilinear_kernel(const uint8_
     }
 }
 
-void launch_resize_image_bilinear(const uint8_t* d_src, int channels, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w, hipStream_t s) {
+void launch_resize_image_bilinear_batch(const uint8_t* d_src, int count, int channels, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w, hipStream_t s) {
+    ANH_REQUIRE(count >= 1, "resize_image: the batch needs at least one image");
     ANH_REQUIRE(channels == 1 || channels == 3, "resize_image: 1 or 3 channels");
     ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1, "resize_image: empty image");
     const int units = 1 + (dst_w + kResizeImagePixels - 1) / kResizeImagePixels + 1;   // head unit + full units (+1: a head shifts the last one)
     const int chunks = (units + 255) / 256;
-    const int64_t items = (int64_t)dst_h * chunks;
+    const int64_t items = (int64_t)count * dst_h * chunks;
     const int blocks = (int)std::min<int64_t>(items, 256 * 16);   // bounded grid-stride: at most 16 workgroups per CU
     if (channels == 3) hipLaunchKernelGGL(resize_image_bilinear_kernel<3>, dim3(blocks), dim3(256), 0, s, d_src, src_h, src_w, d_dst, dst_h, dst_w, chunks, items);
     else hipLaunchKernelGGL(resize_image_bilinear_kernel<1>, dim3(blocks), dim3(256), 0, s, d_src, src_h, src_w, d_dst, dst_h, dst_w, chunks, items);
     HIP_CHECK(hipGetLastError());
+}
+void launch_resize_image_bilinear(const uint8_t* d_src, int channels, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w, hipStream_t s) {
+    launch_resize_image_bilinear_batch(d_src, 1, channels, src_h, src_w, d_dst, dst_h, dst_w, s);
 }
 
 // dlib::resize_image + interpolate_nearest_neighbor [UPSTREAM-UNVERIFIED], as annonet_host.h restates it (resize_label_image): the source
 // column of output column c is floor(c * x_scale + 0.5) in double, the same for rows.  The output is the large side (the original-size
 // map), so it leaves as 16-byte stores of eight labels; the source is 1/factor^2 of it and is re-read from cache.
 //
-// A work item is (band of kResizeLabelRows output rows, chunk of 256 * 8 output columns).  The workgroup computes the source columns of
+// A work item is (image, band of kResizeLabelRows output rows, chunk of 256 * 8 output columns): the `count` maps of a batch lie back
+// to back, [count][rows][cols]; a band never leaves its map, and a map's start is any even address.  The workgroup computes the source columns of
 // its chunk once, into LDS, and then walks the rows of the band.  A lane owns eight consecutive labels that start on a 16-byte boundary
 // of the destination; where a row starts between boundaries (odd widths), its lanes shift left by `back` labels (0..7), which is why the
 // table starts seven columns before the chunk.  Partial units (row ends) go out label by label.
 constexpr int kResizeLabelRows = 32, kResizeLabelCols = 256 * 8;
-__global__ __launch_bounds__(256) void resize_labels_nearest_kernel(const uint16_t* __restrict__ src, int in_nr, int in_nc, uint16_t* __restrict__ dst, int out_nr, int out_nc,
-                                                                     int chunks, int64_t items) {
+__global__ __launch_bounds__(256) void resize_labels_nearest_kernel(const uint16_t* __restrict__ src_all, int in_nr, int in_nc, uint16_t* __restrict__ dst_all, int out_nr, int out_nc,
+                                                                     int bands, int chunks, int64_t items) {
     __shared__ int sx[kResizeLabelCols + 8];
     const double x_scale = (in_nc - 1) / (double)max(out_nc - 1, 1), y_scale = (in_nr - 1) / (double)max(out_nr - 1, 1);
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int band = (int)(item / chunks), chunk = (int)(item - (int64_t)band * chunks);
+        const int64_t band_all = item / chunks;   // band of the whole batch
+        const int chunk = (int)(item - band_all * chunks);
+        const int64_t img = band_all / bands;
+        const int band = (int)(band_all - img * bands);
+        const uint16_t* src = src_all + img * in_nr * in_nc;
+        uint16_t* dst = dst_all + img * out_nr * out_nc;
         const int col0 = chunk * kResizeLabelCols - 7;   // column of sx[0]
         __syncthreads();   // the previous item's rows are done with the table
         for (int j = threadIdx.x; j < kResizeLabelCols + 7; j += 256) {
@@ -2519,14 +2536,19 @@ __global__ __launch_bounds__(256) void resize_labels_nearest_kernel(const uint16
     }
 }
 
-void launch_resize_labels_nearest(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w, hipStream_t s) {
+void launch_resize_labels_nearest_batch(const uint16_t* d_src, int count, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w, hipStream_t s) {
+    ANH_REQUIRE(count >= 1, "resize_labels: the batch needs at least one label image");
     ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1, "resize_labels: empty label image");
     ANH_REQUIRE((reinterpret_cast<uintptr_t>(d_dst) & 1) == 0 && (reinterpret_cast<uintptr_t>(d_src) & 1) == 0, "resize_labels: label maps must be 2-byte aligned");
     const int chunks = (dst_w + 7 + kResizeLabelCols - 1) / kResizeLabelCols;   // + 7: the shift of a row that starts off a 16-byte boundary
-    const int64_t items = (int64_t)((dst_h + kResizeLabelRows - 1) / kResizeLabelRows) * chunks;
+    const int bands = (dst_h + kResizeLabelRows - 1) / kResizeLabelRows;
+    const int64_t items = (int64_t)count * bands * chunks;
     const int blocks = (int)std::min<int64_t>(items, 256 * 16);
-    hipLaunchKernelGGL(resize_labels_nearest_kernel, dim3(blocks), dim3(256), 0, s, d_src, src_h, src_w, d_dst, dst_h, dst_w, chunks, items);
+    hipLaunchKernelGGL(resize_labels_nearest_kernel, dim3(blocks), dim3(256), 0, s, d_src, src_h, src_w, d_dst, dst_h, dst_w, bands, chunks, items);
     HIP_CHECK(hipGetLastError());
+}
+void launch_resize_labels_nearest(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w, hipStream_t s) {
+    launch_resize_labels_nearest_batch(d_src, 1, src_h, src_w, d_dst, dst_h, dst_w, s);
 }
 
 }  // namespace anh

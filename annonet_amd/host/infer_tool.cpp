@@ -8,7 +8,8 @@
 // excluding the first image: average = ... ms, max = ... ms", both confusion matrices), the files it reads (annonet.dnn,
 // <image>_mask.png) and writes (<image>_result.png), and its exit codes (2 for option errors, 1 otherwise).
 // Extensions: --precision fp32|bf16, --devices 0,1,... (tile lists sharded over several GPUs from this one process), --dnn <file>,
-// --host-resize, --image-batch N (consecutive images of one size go through annonet_infer_batch() together).  A net with a downscaling factor other than 1: the image goes to the GPU at its original size and annonet_infer_scaled()
+// --host-resize, --image-batch N (consecutive images of one size go through annonet_infer_batch() together, or through
+// annonet_infer_scaled_batch() where the GPU resizes).  A net with a downscaling factor other than 1: the image goes to the GPU at its original size and annonet_infer_scaled()
 // shrinks it, infers and blows the label map back up there (the reference does both resizes on the CPU: annonet.cpp:153 in the readers,
 // annonet_infer_main.cpp:413 in the writers); --host-resize keeps them on this program's reader / writer threads.  Same files, same matrices.
 #define ANNONET_HIP_NO_DLIB
@@ -45,7 +46,8 @@ const char* usage_text() {
            "      --dnn file                       trained net (default: annonet.dnn)\n"
            "      --host-resize                    downscaled nets: resize image and label map on the CPU threads, not on the GPU\n"
            "      --image-batch N                  up to N consecutive images of one size run as one batch (default: 1, image by image);\n"
-           "                                       taken when the net's downscaling factor is 1 or with --host-resize; with --devices the\n"
+           "                                       with a downscaled net whose resizes run on the GPU the batch forms on the ORIGINAL size and is\n"
+           "                                       shrunk and blown up there by one launch each; with --devices the\n"
            "                                       images of a batch are dealt out to the GPUs.  A batch's time is charged in equal parts\n"
            "                                       to its images, and \"excluding the first image\" then excludes the first batch\n";
 }
@@ -263,8 +265,9 @@ int run(const Settings& settings) {
             return result;
         };
         // --image-batch N > 1: up to N consecutive samples of one size wait here and go through annonet_infer_batch() together; a sample
-        // of another size flushes them first.  (The images reach the GPU at the net's resolution on this path: factor 1, or --host-resize.)
-        const bool batched = settings.image_batch > 1 && !resize_on_gpu;
+        // of another size flushes them first.  Where the GPU resizes (a factor other than 1 without --host-resize) the samples come at
+        // their ORIGINAL size, the groups form on it and go through annonet_infer_scaled_batch().
+        const bool batched = settings.image_batch > 1;
         std::vector<sample_type> pending;
         auto flush = [&] {
             if (pending.empty()) return;
@@ -272,12 +275,13 @@ int run(const Settings& settings) {
             for (sample_type& s : pending) images.push_back(std::move(s.input_image));
             std::vector<dlib::matrix<uint16_t>> maps;
             const auto t0 = std::chrono::steady_clock::now();
-            annonet_infer_batch(trained.net, images, maps, scratch, gains, detection_levels, tiles);
+            if (resize_on_gpu) annonet_infer_scaled_batch(trained.net, images, trained.downscaling, maps, scratch, gains, detection_levels, tiles);
+            else annonet_infer_batch(trained.net, images, maps, scratch, gains, detection_levels, tiles);
             clock.record_batch(std::chrono::duration_cast<InferenceClock::us>(std::chrono::steady_clock::now() - t0), pending.size());
             for (size_t j = 0; j < pending.size(); ++j) {
                 LabelMapToWrite result = result_for(pending[j]);
                 result.labels = std::move(maps[j]);
-                score(pending[j], result.labels);
+                score(pending[j], resize_on_gpu ? scratch.scaled_result_images[j] : result.labels);
                 writers.submit(std::move(result));
             }
             pending.clear();

@@ -469,6 +469,50 @@ def annonet_infer_scaled_device(net, d_image_ptr, height, width, downscaling_fac
                                         d_labels_ptr, d_scaled_labels_ptr or None, d_blended_ptr or None))
 
 
+def annonet_infer_scaled_batch(net, input_images, downscaling_factor, gains=None, detection_levels=None, tiling_parameters=None, want_scaled=False, want_blended=False):
+    """annonet_infer_scaled over several images of ONE original size in one call (anh_infer_scaled_batch): one batched shrink, the
+    forward batches of annonet_infer_batch at the net's resolution, one batched blow-up.  Returns the list of original-size label maps,
+    then (when asked for) the list of maps at the net's resolution and the list of blended class planes at the net's resolution.
+    want_scaled / want_blended may also be lists of booleans, one per image (None where not asked for).  Every image's results equal
+    annonet_infer_scaled() of that image alone, bit for bit."""
+    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in input_images]
+    imgs = [im[:, :, None] if im.ndim == 2 else im for im in imgs]
+    n = len(imgs)
+    K = net.cfg.classes
+    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
+    d = np.ascontiguousarray(detection_levels, dtype=np.float64) if detection_levels is not None else None
+    if g is not None and g.size != K or d is not None and d.size != K:
+        raise AnnonetHipError(1, "gains / detection levels need one value per class")
+    if n and any(im.shape != imgs[0].shape for im in imgs):
+        raise AnnonetHipError(1, "the images of a batch must have one size and channel count")
+    if n and imgs[0].shape[2] != net.cfg.in_channels:
+        raise AnnonetHipError(1, "channel count does not match the net input")
+    H, W = imgs[0].shape[:2] if n else (0, 0)
+    sh, sw = scaled_dims(H, W, downscaling_factor) if n else (0, 0)
+    per_image = lambda want: list(want) if isinstance(want, (list, tuple)) else [bool(want)] * n
+    ws, wb = per_image(want_scaled), per_image(want_blended)
+    res = [np.empty((H, W), np.uint16) for _ in range(n)]
+    sc = [np.empty((sh, sw), np.uint16) if w else None for w in ws]
+    bl = [np.empty((K, sh, sw), np.float32) if w else None for w in wb]
+    ptrs = lambda arrays: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a is not None else None for a in arrays])
+    tp = tiling_parameters._c() if tiling_parameters is not None else None
+    check(net.L.anh_infer_scaled_batch(net.h, ptrs(imgs), n, H, W, downscaling_factor, _ptr(g), _ptr(d), C.byref(tp) if tp is not None else None,
+                                       ptrs(res), ptrs(sc) if any(ws) else None, ptrs(bl) if any(wb) else None))
+    out = (res,) + ((sc,) if any(ws) or want_scaled else ()) + ((bl,) if any(wb) or want_blended else ())
+    return out if len(out) > 1 else res
+
+
+def annonet_infer_scaled_batch_device(net, d_images_ptr, n, height, width, downscaling_factor, d_labels_ptr, d_scaled_labels_ptr=0, d_blended_ptr=0, gains=None,
+                                      tiling_parameters=None):
+    """annonet_infer_scaled_batch with the original-size images [n,H,W,C], the original-size label maps [n,H,W] and (optionally) the maps
+    [n,sh,sw] and the planes [n,K,sh,sw] at the net's resolution resident in HBM (device pointers as ints); enqueued on the handle's
+    stream, not synchronised."""
+    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
+    tp = tiling_parameters._c() if tiling_parameters is not None else None
+    check(net.L.anh_infer_scaled_batch_device(net.h, d_images_ptr, n, height, width, downscaling_factor, _ptr(g), C.byref(tp) if tp is not None else None,
+                                              d_labels_ptr, d_scaled_labels_ptr or None, d_blended_ptr or None))
+
+
 def _through_device(src, out_shape, dtype, prefill, launch):
     """host array -> HBM -> `launch(src_ptr, dst_ptr, stream)` -> host array (torch moves the bytes)"""
     import torch
@@ -497,6 +541,29 @@ def resize_labels(lab, out_w, out_h, prefill=None):
     L = _lib.lib()
     return _through_device(a, (out_h, out_w), np.uint16, prefill,
                            lambda s, d, st: check(L.anh_resize_labels_device(s, a.shape[0], a.shape[1], d, out_h, out_w, st)))
+
+
+def resize_image_batch(images, out_h, out_w, prefill=None):
+    """The device's bilinear resize over a batch by ONE launch (anh_resize_image_batch_device): host u8 images [n,H,W] / [n,H,W,1] /
+    [n,H,W,3] -> [n,out_h,out_w(,C)]; `prefill` as for resize_image."""
+    a = np.ascontiguousarray(images, dtype=np.uint8)
+    if a.ndim not in (3, 4) or a.shape[0] < 1:
+        raise AnnonetHipError(1, "resize_image_batch: an array [n,H,W] or [n,H,W,C] with n >= 1")
+    c = 1 if a.ndim == 3 else a.shape[3]
+    L = _lib.lib()
+    return _through_device(a, (a.shape[0], out_h, out_w) + a.shape[3:], np.uint8, prefill,
+                           lambda s, d, st: check(L.anh_resize_image_batch_device(s, a.shape[0], c, a.shape[1], a.shape[2], d, out_h, out_w, st)))
+
+
+def resize_labels_batch(maps, out_w, out_h, prefill=None):
+    """The device's nearest-neighbour resize over a batch by ONE launch (anh_resize_labels_batch_device): host u16 label maps [n,H,W]
+    -> [n,out_h,out_w]; target width, then target height, as for resize_labels."""
+    a = np.ascontiguousarray(maps, dtype=np.uint16)
+    if a.ndim != 3 or a.shape[0] < 1:
+        raise AnnonetHipError(1, "resize_labels_batch: an array [n,H,W] with n >= 1")
+    L = _lib.lib()
+    return _through_device(a, (a.shape[0], out_h, out_w), np.uint16, prefill,
+                           lambda s, d, st: check(L.anh_resize_labels_batch_device(s, a.shape[0], a.shape[1], a.shape[2], d, out_h, out_w, st)))
 
 
 def argmax_device(net, d_blended_ptr, height, width, row0, row1, d_labels_ptr, gains=None):

@@ -205,6 +205,28 @@ int anh_infer_scaled(anh_runtime* h, const uint8_t* image_hwc, int height, int w
 int anh_infer_scaled_device(anh_runtime* h, const uint8_t* d_image_hwc, int height, int width, double downscaling_factor,
                             const double* gains, const anh_tiling_params* tiling,
                             uint16_t* d_result_labels, uint16_t* d_scaled_labels, float* d_blended);
+/* ---- downscaled inference over n >= 1 images of ONE original size (anh_infer_scaled composed with anh_infer_batch) ----
+ * the two resizes over `count` images that lie back to back, [count][h][w][C] and [count][h][w], by ONE launch each: every image is
+ * resized on its own (no row or column reads a neighbouring image) and equals what the single-image call gives for it */
+int anh_resize_image_batch_device(const uint8_t* d_src_hwc, int count, int channels, int src_h, int src_w,
+                                  uint8_t* d_dst_hwc, int dst_h, int dst_w, void* hip_stream);
+int anh_resize_labels_batch_device(const uint16_t* d_src, int count, int src_h, int src_w,
+                                   uint16_t* d_dst, int dst_h, int dst_w, void* hip_stream);
+/* n originals up, ONE batched shrink, the forward batches of anh_infer_batch at the net's resolution (anh_scaled_dims), the detection-level
+ * filter per image at the net's resolution, ONE batched blow-up, n original-size maps down.  results[i] (height x width) equals, bit for
+ * bit, what anh_infer_scaled returns for image i alone.  scaled_labels / blended_out: NULL, or n pointers of which each may be NULL:
+ * scaled_labels[i] is the map at the net's resolution, blended_out[i] K planes at the net's resolution.  downscaling_factor == 1 is
+ * exactly anh_infer_batch (the scaled maps are copies of the results).  Everything the call needs is reserved before its first kernel
+ * or copy: a batch that does not fit returns ANH_ERR_OOM and leaves the handle usable.  On a handle with R replicas replica r shrinks,
+ * infers and blows up the images anh_shard_range(n, R, r) on its own; n < R goes image by image through anh_infer_scaled. */
+int anh_infer_scaled_batch(anh_runtime* h, const uint8_t* const* images_hwc, int n, int height, int width, double downscaling_factor,
+                           const double* gains, const double* detection_levels, const anh_tiling_params* tiling,
+                           uint16_t* const* results, uint16_t* const* scaled_labels, float* const* blended_out);
+/* the same with everything resident in HBM on the handle's first device, enqueued on the handle's stream without synchronising:
+ * d_images_hwc [n][H][W][C], d_results [n][H][W]; d_scaled_labels [n][sh][sw] and d_blended [n][K][sh][sw] are optional (NULL) */
+int anh_infer_scaled_batch_device(anh_runtime* h, const uint8_t* d_images_hwc, int n, int height, int width, double downscaling_factor,
+                                  const double* gains, const anh_tiling_params* tiling,
+                                  uint16_t* d_results, uint16_t* d_scaled_labels, float* d_blended);
 /* label rows [row0, row1) of device-resident blended planes (find_label, annonet_infer.cpp:170-185): the second half of a
    sharded annonet_infer(), run after the ranks have exchanged the plane sums of their overlapping tiles */
 int anh_argmax_device(anh_runtime* h, const float* d_blended, int height, int width, int row0, int row1, const double* gains, uint16_t* d_result);

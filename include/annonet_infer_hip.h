@@ -29,6 +29,7 @@ struct annonet_infer_temp {  // annonet_infer.h:26-32; the GPU path keeps its sc
     std::vector<dlib::matrix<float>> blended_output;  // filled when keep_blended_output is set (see above for its default)
     bool keep_blended_output = annonet_hip_keep_blended_default();
     dlib::matrix<uint16_t> scaled_result_image;       // annonet_infer_scaled: the label map at the net's resolution, filled on every scaled call
+    std::vector<dlib::matrix<uint16_t>> scaled_result_images;   // annonet_infer_scaled_batch: one such map per image, filled on every call
 };
 
 inline void annonet_infer(NetPimpl::RuntimeNet& net, const NetPimpl::input_type& input_image, dlib::matrix<uint16_t>& result_image,
@@ -120,6 +121,51 @@ inline void annonet_infer_scaled(NetPimpl::RuntimeNet& net, const NetPimpl::inpu
     NetPimpl::check(anh_infer_scaled(net.handle(), reinterpret_cast<const uint8_t*>(&*input_image.begin()), H, W, downscaling_factor,
                                      gains.empty() ? nullptr : gains.data(), detection_levels.empty() ? nullptr : detection_levels.data(), &tp,
                                      &*result_image.begin(), &*temp.scaled_result_image.begin(), temp.keep_blended_output ? planes.data() : nullptr));
+    if (temp.keep_blended_output) {
+        temp.blended_output.resize(K);
+        for (int k = 0; k < K; ++k) {
+            temp.blended_output[k].set_size(sh, sw);
+            std::copy(planes.begin() + (size_t)k * sh * sw, planes.begin() + (size_t)(k + 1) * sh * sw, temp.blended_output[k].begin());
+        }
+    }
+}
+
+// annonet_infer_scaled() over several images of ONE original size in one call (anh_infer_scaled_batch): one batched shrink, the forward
+// batches of annonet_infer_batch() at the net's resolution, one batched blow-up.  result_images[i] (original size) and
+// temp.scaled_result_images[i] (the net's resolution) belong to input_images[i] and equal, bit for bit, what annonet_infer_scaled() gives
+// for that image alone.  temp.blended_output keeps its keep_blended_output rule and holds the planes of the LAST image at the net's
+// resolution, as it would after a loop of annonet_infer_scaled() calls.
+inline void annonet_infer_scaled_batch(NetPimpl::RuntimeNet& net, const std::vector<NetPimpl::input_type>& input_images, double downscaling_factor,
+                                       std::vector<dlib::matrix<uint16_t>>& result_images, annonet_infer_temp& temp,
+                                       const std::vector<double>& gains = std::vector<double>(), const std::vector<double>& detection_levels = std::vector<double>(),
+                                       const tiling::parameters& tiling_parameters = tiling::parameters()) {
+    anh_net_config cfg;
+    NetPimpl::check(anh_runtime_config(net.handle(), &cfg));
+    if (input_images.empty()) throw std::runtime_error("annonet_infer_scaled_batch: the batch needs at least one image");
+    const int K = cfg.classes, n = (int)input_images.size(), H = (int)input_images[0].nr(), W = (int)input_images[0].nc();
+    if (!gains.empty() && (int)gains.size() != K) throw std::runtime_error("annonet_infer_scaled_batch: one gain per class expected");
+    if (!detection_levels.empty() && (int)detection_levels.size() != K) throw std::runtime_error("annonet_infer_scaled_batch: one detection level per class expected");
+    int sh = 0, sw = 0;
+    NetPimpl::check(anh_scaled_dims(H, W, downscaling_factor, &sh, &sw));
+    std::vector<const uint8_t*> images((size_t)n);
+    std::vector<uint16_t*> results((size_t)n), scaled((size_t)n);
+    std::vector<float*> planes_of((size_t)n, nullptr);
+    result_images.resize((size_t)n);
+    temp.scaled_result_images.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if ((int)input_images[i].nr() != H || (int)input_images[i].nc() != W) throw std::runtime_error("annonet_infer_scaled_batch: the images of a batch must have one size");
+        images[i] = reinterpret_cast<const uint8_t*>(&*input_images[i].begin());
+        result_images[i].set_size(H, W);
+        results[i] = &*result_images[i].begin();
+        temp.scaled_result_images[i].set_size(sh, sw);
+        scaled[i] = &*temp.scaled_result_images[i].begin();
+    }
+    std::vector<float> planes;
+    if (temp.keep_blended_output) { planes.resize((size_t)K * sh * sw); planes_of[n - 1] = planes.data(); }
+    anh_tiling_params tp{tiling_parameters.max_tile_width, tiling_parameters.max_tile_height, tiling_parameters.overlap_x, tiling_parameters.overlap_y};
+    NetPimpl::check(anh_infer_scaled_batch(net.handle(), images.data(), n, H, W, downscaling_factor, gains.empty() ? nullptr : gains.data(),
+                                           detection_levels.empty() ? nullptr : detection_levels.data(), &tp, results.data(), scaled.data(),
+                                           temp.keep_blended_output ? planes_of.data() : nullptr));
     if (temp.keep_blended_output) {
         temp.blended_output.resize(K);
         for (int k = 0; k < K; ++k) {
