@@ -1037,6 +1037,13 @@ int anh_infer_scaled_batch(anh_runtime* h, const uint8_t* const* images, int n, 
 int anh_runtime_set_stream(anh_runtime* h, void* s) { return guarded([&] { ANH_REQUIRE(h, "null handle"); ANH_REQUIRE(h->reps.size() == 1, "a handle that drives several devices keeps its own streams"); h->reps.engine(0).set_stream((hipStream_t)s); }); }
 int anh_runtime_get_stream(anh_runtime* h, void** s) { return guarded([&] { ANH_REQUIRE(h && s, "null argument"); *s = (void*)h->reps.engine(0).stream; }); }
 int anh_runtime_stores_activations(anh_runtime* h, int* yes) { return guarded([&] { ANH_REQUIRE(h && yes, "null argument"); *yes = h->reps.engine(0).infer_post ? 1 : 0; }); }
+int anh_runtime_layer_tensor(anh_runtime* h, int layer, float* out, int64_t capacity, int dims4[4]) {
+    return guarded([&] {
+        ANH_REQUIRE(h && dims4, "null argument");
+        DeviceScope scope(h->reps.device_of(0));
+        h->reps.engine(0).layer_tensor(layer, 0, out, capacity, dims4);
+    });
+}
 int anh_runtime_synchronize(anh_runtime* h) {
     return guarded([&] { ANH_REQUIRE(h, "null handle"); h->reps.for_all([](size_t, Engine& e) { e.synchronize(); }); });
 }

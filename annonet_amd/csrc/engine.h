@@ -51,6 +51,7 @@ struct LayerState {
     float* coef = nullptr;  // bn backward coefficients [3][C] of this layer (its own slot: two streams read them)
     int n = 0, h_in = 0, w_in = 0, h = 0, w = 0;
     bool dact_written = false;
+    bool stored = false;   // inference: the last pass wrote `raw` at the planned dimensions (Engine::layer_tensor reads nothing else)
     const void* da_alias = nullptr;   // backward: da of this layer lives in ANOTHER layer's buffer (skip gradient written once); its apply pass reads it from there
     // backward bookkeeping: a layer's da is final once all its consumers' backward-data convs have written it; the conv
     // that writes it last may also leave the dgamma / dbeta partial sums (fused bn backward reduction)
@@ -111,6 +112,9 @@ class Engine {
     void apply_update(double lr, double weight_decay, double momentum, double grad_scale, unsigned long bn_window, unsigned long long* loss_post = nullptr, unsigned int loss_tag = 0);
     double read_loss();  // synchronises
     int read_error_flag_and_clear();
+    // training net: raw conv output (which = 0) or the gradient w.r.t. the layer's activation (which = 1).  Inference net: which = 0 only, the
+    // tensor a bn layer stored in the LAST pass; "tensor not available" for a layer that pass did not store (the layer under a head in the
+    // epilogue, the head itself, any layer before the first pass or after the dimensions were planned anew).
     void layer_tensor(int layer, int which, float* out_host, int64_t capacity, int dims[4]);
 
     // ---- tiled inference: annonet_infer.cpp:42-214 with image, blended planes and labels resident in HBM ----

@@ -284,6 +284,7 @@ void Engine::plan_dims_unguarded(int n, int h, int w) {
                 "input size is not a valid net input dimension (see GetRecommendedInputDimension)");
     const size_t es = elem_size(dtype);
     size_t bn_need = 0;
+    for (LayerState& s : ls) s.stored = false;   // the buffers may move or change shape: what an earlier inference pass left is no longer readable
     for (size_t li = 0; li < spec.layers.size(); ++li) {
         const anh_layer_desc& L = spec.layers[li];
         LayerState& s = ls[li];
@@ -497,6 +498,7 @@ void Engine::run_conv_forward(int li, const Src& image, bool training_pass, floa
         }
     }
     conv_dispatch(a, (std::string("fwd_") + layer_tag(li, L)).c_str(), flops, bytes);
+    if (!training_pass) s.stored = L.has_bn && !a.head_out;   // (under a head in the epilogue the logits go to memory, not the activation)
     if (table_layer) {   // no finalize launch: only this step's running-statistics bookkeeping, applied by the fold job
         s.fold_running = update_running_in_forward;
         if (update_running_in_forward) {
@@ -884,6 +886,7 @@ void Engine::layer_tensor(int layer, int which, float* out_host, int64_t capacit
     ANH_REQUIRE(layer >= 0 && layer < (int)ls.size(), "layer index out of range");
     const anh_layer_desc& L = spec.layers[layer];
     const LayerState& s = ls[layer];
+    if (!training) ANH_REQUIRE(which == 0 && L.has_bn && s.stored, "tensor not available");
     dims[0] = s.n; dims[1] = s.h; dims[2] = s.w; dims[3] = L.cout;
     const int64_t elems = (int64_t)s.n * s.h * s.w * L.cout;
     if (!out_host) return;

@@ -330,6 +330,15 @@ class RuntimeNet(_Profiled):
         check(self.L.anh_runtime_stores_activations(self.h, C.byref(yes)))
         return bool(yes.value)
 
+    def layer_tensor(self, layer):
+        """fp32 [n,h,w,c]: the tensor bn layer `layer` stored in the handle's last inference pass (anh_runtime_layer_tensor); raises
+        for a layer that pass did not store"""
+        dims = (C.c_int * 4)()
+        check(self.L.anh_runtime_layer_tensor(self.h, layer, None, 0, dims))
+        out = np.empty(tuple(dims), np.float32)
+        check(self.L.anh_runtime_layer_tensor(self.h, layer, _ptr(out), out.size, dims))
+        return out
+
 
 def annonet_infer(net, input_image, gains=None, detection_levels=None, tiling_parameters=None, want_blended=False):
     """annonet_infer() (annonet_infer.h:34-42): returns the u16 label image (and the blended class planes)."""

@@ -240,6 +240,10 @@ int anh_runtime_get_stream(anh_runtime* h, void** hip_stream);
  * *yes = the form of the handle's LAST inference pass (parity tests pick the matching CPU restatement; ANH_INFER_POST_ACT=0 forces
  * the second form). */
 int anh_runtime_stores_activations(anh_runtime* h, int* yes);
+/* parity tap: the tensor bn layer `layer` stored in the handle's LAST inference pass (replica 0), as fp32 NHWC; out = NULL asks for the
+ * dimensions only.  Fails ("tensor not available") for a layer that pass did not store: the head, the layer whose epilogue ran the head,
+ * every layer before the first pass.  Synchronises the handle's stream. */
+int anh_runtime_layer_tensor(anh_runtime* h, int layer, float* out, int64_t capacity, int dims4[4]);
 int anh_runtime_synchronize(anh_runtime* h);
 
 /* ---- TrainingNet (annonet_train_main.cpp:396-410) ---- */
