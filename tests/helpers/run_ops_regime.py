@@ -3,7 +3,8 @@ shrinks the persistent kernels' grids (ANH_WS_WGS / ANH_WGRAD_WGS / ANH_STEM_BLO
 process), so that every workgroup walks many (pixel tile, slab) items: ring buffers wrap, the XCD-band walk (grid 8) and the
 grid-stride walk (grid 3) both run, the producer-issued stores / sums of "two items ago" and the tile-ahead old-value prefetch
 reach their steady state.  The bars are those of test_gpu_ops.py (one bf16 ulp on <= 2 % of the elements against orc_op_*; filter
-gradients rtol 2e-3; fused sums 2e-5 / 1e-4 of float64 sums over the stored tensor) — the functions themselves are reused.
+gradients rtol 2e-3; fused sums 2e-5 / 1e-4 of float64 sums over the stored tensor) — the functions themselves are reused — and, next
+to them, the float64 bars of tests/train_conv_ref.py with the kernel-form assertions of tests/test_gpu_train_conv.py.
 The table forms of the conv epilogues and prologues (tests/test_gpu_train_ops.py) run in the same loop: with 3 and 8 workgroups the
 replica choice and the finish's ticket run with fewer workgroups than a table has replicas.
 "loops" is the same idea for the kernels that are not convolutions: the process sets ANH_HEAD_BLOCKS / ANH_APPLY_BLOCKS to 2, so every
@@ -23,6 +24,7 @@ import numpy as np  # noqa: E402
 
 import annonet_amd as aa  # noqa: E402
 import test_gpu_ops as ops  # noqa: E402
+import test_gpu_train_conv as tconv  # noqa: E402
 import test_gpu_train_ops as tops  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 
@@ -38,6 +40,9 @@ REGIME = [
     ((0, 3, 2, 0, 64, 128), 1, 41, 71),
     ((1, 3, 2, 0, 128, 64), 1, 20, 35),     # cont: GeoUp forward / GeoDown backward-data
     ((1, 3, 2, 0, 64, 32), 2, 23, 33),
+    ((0, 3, 1, 1, 256, 256), 1, 17, 70),    # levels = 3: four workgroup groups of 64 channels, the filter gradient in two tile groups —
+    ((0, 3, 2, 0, 128, 256), 1, 35, 71),    # with 3 / 8 workgroups every one of them walks several items of each
+    ((1, 3, 2, 0, 256, 128), 1, 17, 35),
 ]
 # (b) full-width shapes at the benchmark's real plane size (8 tiles across a 227-pixel row, ragged last tile, band walk over 464 tiles)
 FULL = [
@@ -92,8 +97,14 @@ def main():
         for prologue in (0, 1, 2):
             bad += run("forward p%d %s" % (prologue, tag), ops.test_conv_forward, desc, n, h, w, prologue, BF)
         bad += run("backward-data " + tag, ops.test_conv_backward_data, desc, n, h, w, BF)
-        for prologue in (0, 2):
+        for prologue in (0, 1, 2):
             bad += run("backward-filter p%d %s" % (prologue, tag), ops.test_conv_backward_filter, desc, n, h, w, prologue, BF)
+        # the float64 bars of tests/train_conv_ref.py (element bars in full, the sequential-emulation bar on its subset) and the kernel form
+        for prologue in (0, 1, 2):
+            bad += run("float64 forward p%d %s" % (prologue, tag), tconv.test_forward, desc, n, h, w, prologue)
+        bad += run("float64 backward-data " + tag, tconv.test_backward_data, desc, n, h, w)
+        for prologue in (0, 1, 2):
+            bad += run("float64 backward-filter p%d %s" % (prologue, tag), tconv.test_filter_gradient, desc, n, h, w, prologue)
         for prologue in (1, 2):
             bad += run("forward + bn statistics p%d %s" % (prologue, tag), ops.test_conv_forward_fused_bn_statistics, desc, n, h, w, prologue)
         for accumulate in (False, True):
@@ -111,6 +122,9 @@ def main():
         bad += run("stem filter gradient with dy in the kernel", ops.test_stem_filter_gradient_computes_dy_in_kernel)
         bad += run("stem filter gradient", ops.test_conv_backward_filter, *stem, 0, BF)
         bad += run("stem forward into a table", tops.test_stem_forward_into_a_table, stem)
+        bad += run("float64 stem forward on the image", tconv.test_stem_forward_on_the_image, *stem)
+        bad += run("float64 stem filter gradient with dy in the kernel", tconv.test_stem_filter_gradient_with_dy_formed_in_the_kernel, 3, 45, 70, 3)
+        bad += run("float64 stem filter gradient", tconv.test_filter_gradient, *stem, 0)
     print("failed cases: %d" % bad, flush=True)
     sys.exit(1 if bad else 0)
 

@@ -7,6 +7,8 @@
                       on at most 2% of the elements; backward-filter rtol 2e-3 against double accumulation.
 Shapes cover every layer kind of the net (stem 5x5 on 3 channels, 3x3 s1, 3x3 s2, transposed 3x3 s2, 1x1 head), odd
 sizes, ragged tile edges, and the prologue kinds (raw / bn+relu / bn+relu with skip add).
+The oracle is itself a bf16 emulation; tests/test_gpu_train_conv.py holds the same bf16 kernels to float64 with per-element bars, rounding
+statistics and an assertion of the kernel form per case.
 """
 import numpy as np
 import pytest
