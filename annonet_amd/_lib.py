@@ -99,6 +99,12 @@ class OpHead(C.Structure):   # anh_op_head
                [("error_flag", C.c_int), ("ticket", C.c_int64), ("workgroups", C.c_int)]
 
 
+class Region(C.Structure):   # anh_region
+    _fields_ = [("blob", C.c_uint32), ("label", C.c_uint16), ("detected", C.c_uint16)] + \
+               [(n, C.c_int32) for n in ("left", "top", "right", "bottom", "first_row", "first_col")] + \
+               [("area", C.c_int64), ("seeds", C.c_int64), ("peak", C.c_float)]
+
+
 class TilingParams(C.Structure):
     _fields_ = [("max_tile_width", C.c_int), ("max_tile_height", C.c_int), ("overlap_x", C.c_int), ("overlap_y", C.c_int)]
 
@@ -134,6 +140,9 @@ _SIGNATURES = {  # ConvDesc / OpInput are defined above
     "anh_runtime_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "anh_runtime_forward_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "anh_infer": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), _P, _P]),
+    "anh_label_blobs_device": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(C.c_uint32)]),
+    "anh_regions_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
+    "anh_infer_regions": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), _P, _P, _P, C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
     "anh_infer_device": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(TilingParams), C.POINTER(Tile), C.c_size_t, _P, _P]),
     "anh_infer_batch": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), C.POINTER(_P), C.POINTER(_P)]),
     "anh_infer_batch_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(TilingParams), _P, _P]),

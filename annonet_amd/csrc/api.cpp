@@ -719,6 +719,65 @@ int anh_infer(anh_runtime* h, const uint8_t* image, int height, int width, const
     });
 }
 
+// ---- connected blobs and the region table (Engine::label_blobs / regions) ----
+namespace {
+void require_blob_map_size(int height, int width) {
+    ANH_REQUIRE(height >= 1 && width >= 1, "empty label map");
+    ANH_REQUIRE((int64_t)height * width < ((int64_t)1 << 31), "blob labelling is limited to height * width < 2^31 pixels");
+}
+}  // namespace
+
+int anh_label_blobs_device(anh_runtime* h, const uint16_t* d_labels, int height, int width, uint32_t* d_blobs, uint32_t* count) {
+    return guarded([&] {
+        require_blob_map_size(height, width);   // first: a size beyond the limit is refused whatever else is wrong
+        ANH_REQUIRE(h && d_labels && d_blobs && count, "null argument");
+        DeviceScope scope(h->reps.device_of(0));
+        *count = h->reps.engine(0).label_blobs(d_labels, height, width, d_blobs);
+    });
+}
+
+int anh_regions_device(anh_runtime* h, uint16_t* d_labels, const float* d_blended, int classes, int height, int width, const double* detection_levels,
+                       int apply_filter, uint32_t* d_blobs, anh_region** regions, size_t* n_regions) {
+    return guarded([&] {
+        require_blob_map_size(height, width);
+        ANH_REQUIRE(classes >= 1 && classes <= 65535, "regions: the class count must be within 1..65535");
+        ANH_REQUIRE(h && d_labels && d_blended && regions && n_regions, "null argument");
+        DeviceScope scope(h->reps.device_of(0));
+        (void)h->reps.engine(0).regions(d_labels, d_blended, classes, height, width, detection_levels, apply_filter != 0, d_blobs, regions, n_regions);
+    });
+}
+
+int anh_infer_regions(anh_runtime* h, const uint8_t* image, int height, int width, const double* gains, const double* detection_levels,
+                      const anh_tiling_params* tiling, uint16_t* result, uint32_t* blobs, float* blended_out, anh_region** regions, size_t* n_regions) {
+    return guarded([&] {
+        require_blob_map_size(height, width);
+        ANH_REQUIRE(h && image && result && regions && n_regions, "null argument");
+        DeviceScope scope(h->reps.device_of(0));
+        Engine& e = h->reps.engine(0);   // the blobs are those of the WHOLE label map: replica 0 alone, as anh_infer's filter
+        const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
+        const size_t plane = (size_t)height * width;
+        std::vector<anh_tile> tiles = tiles_for(tiling, width, height);
+        (void)detection_requested(detection_levels, K);   // negative levels are refused before anything is enqueued
+        e.stage_image.reserve(plane * C);
+        e.stage_blended.reserve(plane * K * 4);
+        e.stage_result.reserve(plane * 2);
+        (void)e.reserve_blobs(height, width, K, true);
+        HIP_CHECK(hipMemcpyAsync(e.stage_image.p, image, plane * C, hipMemcpyHostToDevice, e.stream));
+        e.infer_device(e.stage_image.as<uint8_t>(), height, width, gains, tiles, e.stage_result.as<uint16_t>(), e.stage_blended.as<float>(), /*whole_image=*/true);
+        anh_region* table = nullptr;
+        size_t rows = 0;
+        const uint32_t* d_blobs = e.regions(e.stage_result.as<uint16_t>(), e.stage_blended.as<float>(), K, height, width, detection_levels, /*filter=*/true, nullptr, &table, &rows);
+        try {
+            HIP_CHECK(hipMemcpyAsync(result, e.stage_result.p, plane * 2, hipMemcpyDeviceToHost, e.stream));
+            if (blobs) HIP_CHECK(hipMemcpyAsync(blobs, d_blobs, plane * 4, hipMemcpyDeviceToHost, e.stream));
+            if (blended_out) HIP_CHECK(hipMemcpyAsync(blended_out, e.stage_blended.p, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
+            e.synchronize();
+        } catch (...) { std::free(table); throw; }
+        *regions = table;
+        *n_regions = rows;
+    });
+}
+
 // ---- annonet_infer() over several images of one size (Engine::infer_batch_device) ----
 int anh_infer_batch_device(anh_runtime* h, const uint8_t* d_images, int n, int height, int width, const double* gains, const anh_tiling_params* tiling,
                            uint16_t* d_results, float* d_blended) {

@@ -177,6 +177,19 @@ class Engine {
     void resize_labels_batch(const uint16_t* d_src, int count, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w);
     std::vector<float> host_out;
 
+    // ---- connected blobs and the region table (kernels_blobs.hip; annonet_infer.cpp:194-223) ----
+    // scratch of one map of H x W with K detection levels: [parent | block sums | count | levels | seed flags]; own_map: a blob map of the
+    // engine's own as well (the caller gives none).  Nothing is enqueued.
+    struct BlobScratch { int* parent; unsigned* sums; unsigned* count; double* det; uint8_t* flags; };
+    BlobScratch reserve_blobs(int H, int W, int K, bool own_map);
+    DevBuf blob_scratch, blob_map, blob_table;
+    // d_blobs [H][W] = the blob numbers of d_labels; returns blobs + 1.  Synchronises (the count comes back).
+    uint32_t label_blobs(const uint16_t* d_labels, int H, int W, uint32_t* d_blobs);
+    // the table of d_labels' blobs as a malloc'd block of *n rows (the caller owns it); levels_host: K doubles or null; filter: relabel the
+    // blobs without a seed to 0 when a level is positive.  d_blobs may be null.  Returns the blob map it used.  Synchronises twice.
+    uint32_t* regions(uint16_t* d_labels, const float* d_blended, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
+                      anh_region** out, size_t* n);
+
   private:
     void plan_dims(int n, int h, int w);
     void plan_dims_unguarded(int n, int h, int w);

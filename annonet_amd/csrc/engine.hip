@@ -1231,4 +1231,71 @@ void Engine::resize_labels_batch(const uint16_t* d_src, int count, int src_h, in
     prof.end(stream, tok);
 }
 
+// ---- connected blobs and the region table ----
+Engine::BlobScratch Engine::reserve_blobs(int H, int W, int K, bool own_map) {
+    ANH_REQUIRE(H >= 1 && W >= 1, "empty label map");
+    ANH_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), "blob labelling is limited to height * width < 2^31 pixels");
+    const size_t plane = (size_t)H * W;
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t sums_off = up(plane * 4), count_off = sums_off + up(blob_scan_blocks((int64_t)plane) * 4), det_off = count_off + 256;
+    const size_t flags_off = det_off + up((size_t)std::max(K, 1) * sizeof(double));
+    blob_scratch.reserve(flags_off + plane);
+    if (own_map) blob_map.reserve(plane * 4);
+    char* base = blob_scratch.as<char>();
+    return BlobScratch{reinterpret_cast<int*>(base), reinterpret_cast<unsigned*>(base + sums_off), reinterpret_cast<unsigned*>(base + count_off),
+                       reinterpret_cast<double*>(base + det_off), reinterpret_cast<uint8_t*>(base + flags_off)};
+}
+
+uint32_t Engine::label_blobs(const uint16_t* d_labels, int H, int W, uint32_t* d_blobs) {
+    const BlobScratch b = reserve_blobs(H, W, 0, false);
+    const double px = (double)H * W;
+    const int tok = prof.begin(stream, "label_blobs", 0, px * 40.0);
+    launch_blob_label(d_labels, H, W, b.parent, d_blobs, b.sums, b.count, stream);
+    launch_blob_number(b.parent, d_blobs, d_labels, H, W, nullptr, stream);
+    prof.end(stream, tok);
+    uint32_t count = 0;
+    HIP_CHECK(hipMemcpyAsync(&count, b.count, sizeof count, hipMemcpyDeviceToHost, stream));
+    wait_stream(stream, bounded_waits);
+    return count;
+}
+
+uint32_t* Engine::regions(uint16_t* d_labels, const float* d_blended, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
+                          anh_region** out, size_t* n) {
+    ANH_REQUIRE(K >= 1 && K <= 65535, "regions: the class count must be within 1..65535");
+    const BlobScratch b = reserve_blobs(H, W, K, d_blobs == nullptr);   // everything but the table, before the first kernel
+    if (!d_blobs) d_blobs = blob_map.as<uint32_t>();
+    bool positive = false;
+    std::vector<double> levels((size_t)K, 0.0);   // no positive level: zeros (read by the upload below, which the first wait covers)
+    if (levels_host) for (int k = 0; k < K; ++k) { ANH_REQUIRE(levels_host[k] >= 0.0, "detection levels must be >= 0"); positive = positive || levels_host[k] > 0.0; }
+    if (positive) levels.assign(levels_host, levels_host + K);
+    const double px = (double)H * W;
+    int tok = prof.begin(stream, "label_blobs", 0, px * 40.0 + px * 11.0);
+    HIP_CHECK(hipMemcpyAsync(b.det, levels.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice, stream));
+    launch_detection_seeds(d_blended, d_labels, K, H, W, b.det, b.flags, stream);
+    launch_blob_label(d_labels, H, W, b.parent, d_blobs, b.sums, b.count, stream);
+    prof.end(stream, tok);
+    uint32_t count = 0;
+    HIP_CHECK(hipMemcpyAsync(&count, b.count, sizeof count, hipMemcpyDeviceToHost, stream));
+    wait_stream(stream, bounded_waits);
+    ANH_REQUIRE(count >= 1, "blob labelling returned no count");
+    const uint32_t rows = count - 1;
+    // the one reservation whose size is known only now; a failure leaves the handle as it was (the blob map stays un-numbered)
+    if (rows) blob_table.reserve((size_t)rows * sizeof(anh_region));
+    anh_region* host = static_cast<anh_region*>(std::malloc(std::max<size_t>(1, (size_t)rows * sizeof(anh_region))));
+    if (!host) fail(ANH_ERR_OOM, "host allocation of the region table failed");
+    try {
+        anh_region* table = rows ? blob_table.as<anh_region>() : nullptr;
+        tok = prof.begin(stream, "blob_regions", 0, px * 19.0);
+        launch_blob_number(b.parent, d_blobs, d_labels, H, W, table, stream);
+        launch_blob_stats(d_blobs, d_labels, d_blended, K, H, W, b.flags, table, rows, positive, stream);
+        if (filter && positive && rows) launch_blob_filter(d_labels, d_blobs, table, (int64_t)H * W, stream);
+        prof.end(stream, tok);
+        if (rows) HIP_CHECK(hipMemcpyAsync(host, table, (size_t)rows * sizeof(anh_region), hipMemcpyDeviceToHost, stream));
+        wait_stream(stream, bounded_waits);
+    } catch (...) { std::free(host); throw; }
+    *out = host;
+    *n = rows;
+    return d_blobs;
+}
+
 }  // namespace anh

@@ -305,6 +305,23 @@ void launch_crop_weights(const uint16_t* d_labels, const float* d_table, int n, 
 // detection-level filter of annonet_infer() on the device (kernels_generic.hip)
 void run_detection_filter(const float* d_blended, uint16_t* d_labels, int k, int h, int w, const double* d_det, uint8_t* d_flags, int* d_changed,
                           hipStream_t s);
+// the filter's first launch on its own: flags[p] = 1 where pixel p is a detection seed (ANH_DET_SEED_REFERENCE_ORDER honoured); H*W bytes
+void launch_detection_seeds(const float* d_blended, const uint16_t* d_labels, int k, int h, int w, const double* d_det, uint8_t* d_flags, hipStream_t s);
+// connected blobs of a u16 label map [h][w] with h * w < 2^31 (kernels_blobs.hip): 8-connected sets of equal non-zero label, numbered
+// 1, 2, ... in raster order of their first pixel.  No launch waits for another workgroup of the same launch.
+constexpr int kBlobTile = 32;              // side of the tiles the local pass labels in LDS
+size_t blob_scan_blocks(int64_t pixels);   // words of d_sums
+// local, seam, flatten, scan, rank.  Afterwards *d_count = blobs + 1, d_blobs[p] = root(p) + 1 (0: background) and the root's slot of
+// d_parent holds the blob's number: launch_blob_number finishes d_blobs.  d_parent, d_blobs: h * w words each.
+void launch_blob_label(const uint16_t* d_labels, int h, int w, int* d_parent, uint32_t* d_blobs, unsigned* d_sums, unsigned* d_count, hipStream_t s);
+// d_blobs[p] = number of p's blob (0: background); d_table (nullable, one row per blob): every row initialised for launch_blob_stats
+void launch_blob_number(const int* d_numbers, uint32_t* d_blobs, const uint16_t* d_labels, int h, int w, anh_region* d_table, hipStream_t s);
+// area, bounding box, seeds (the flags of launch_detection_seeds counted per blob) and peak margin blended[label] - blended[0] of every blob,
+// by integer atomics; then `detected` (filtering: seeds > 0, else 1) and the peak as a float
+void launch_blob_stats(const uint32_t* d_blobs, const uint16_t* d_labels, const float* d_blended, int k, int h, int w, const uint8_t* d_flags,
+                       anh_region* d_table, uint32_t n_regions, bool filtering, hipStream_t s);
+// labels[p] = 0 where p's blob has no seed: one launch
+void launch_blob_filter(uint16_t* d_labels, const uint32_t* d_blobs, const anh_region* d_table, int64_t pixels, hipStream_t s);
 void launch_reduce_partials(const float* partials, int splits, int64_t nw, float* out, hipStream_t s);
 
 struct BnFoldJobs;

@@ -1908,6 +1908,17 @@ void run_detection_filter(const float* d_blended, uint16_t* d_labels, int k, int
     HIP_CHECK(hipGetLastError());
 }
 
+// The seed launch of run_detection_filter on its own (the region table counts these flags per blob, kernels_blobs.hip).
+void launch_detection_seeds(const float* d_blended, const uint16_t* d_labels, int k, int h, int w, const double* d_det, uint8_t* d_flags, hipStream_t s) {
+    const int64_t pixels = (int64_t)h * w;
+    if (pixels == 0) return;
+    const int blocks = (int)std::min<int64_t>((pixels + 255) / 256, 256 * 16);
+    static const int reference_order = getenv("ANH_DET_SEED_REFERENCE_ORDER") ? atoi(getenv("ANH_DET_SEED_REFERENCE_ORDER")) : 0;
+    if (reference_order) HIP_CHECK(hipMemsetAsync(d_flags, 0, (size_t)pixels, s));
+    hipLaunchKernelGGL(det_seed_kernel, dim3(blocks), dim3(256), 0, s, d_blended, d_labels, k, pixels, d_det, d_flags, reference_order, h, w);
+    HIP_CHECK(hipGetLastError());
+}
+
 // ===================================================================================================
 // launchers
 // ===================================================================================================

@@ -12,6 +12,7 @@
 // annonet_infer_scaled_batch() where the GPU resizes).  A net with a downscaling factor other than 1: the image goes to the GPU at its original size and annonet_infer_scaled()
 // shrinks it, infers and blows the label map back up there (the reference does both resizes on the CPU: annonet.cpp:153 in the readers,
 // annonet_infer_main.cpp:413 in the writers); --host-resize keeps them on this program's reader / writer threads.  Same files, same matrices.
+// --write-regions: annonet_infer_regions() instead of annonet_infer(), and <image>_result_regions.csv beside every result PNG.
 #define ANNONET_HIP_NO_DLIB
 #include "../../include/annonet_infer_hip.h"
 #include "annonet_host.h"
@@ -28,6 +29,7 @@ struct Settings {
     std::vector<int> devices;
     int max_tile_w = 1024, max_tile_h = 1024;   // the reference's GPU-build defaults (:300-303)
     bool host_resize = false;
+    bool write_regions = false;
     int image_batch = 1;
     int readers = (int)std::max(1u, std::thread::hardware_concurrency()), writers = (int)std::max(1u, std::thread::hardware_concurrency());
 };
@@ -45,6 +47,9 @@ const char* usage_text() {
            "      --devices 0,1,...                GPUs this process drives (tile lists are sharded over them)\n"
            "      --dnn file                       trained net (default: annonet.dnn)\n"
            "      --host-resize                    downscaled nets: resize image and label map on the CPU threads, not on the GPU\n"
+           "      --write-regions                  also write <image>_result_regions.csv: one line per DETECTED connected blob of the label map\n"
+           "                                       (class_index,class_name,left,top,right,bottom,area,seeds,peak; boxes in pixels of the net's\n"
+           "                                       resolution).  Images go one by one, and a downscaled net takes the --host-resize route\n"
            "      --image-batch N                  up to N consecutive images of one size run as one batch (default: 1, image by image);\n"
            "                                       with a downscaled net whose resizes run on the GPU the batch forms on the ORIGINAL size and is\n"
            "                                       shrunk and blown up there by one launch each; with --devices the\n"
@@ -73,6 +78,7 @@ Settings read_command_line(int argc, char** argv) {
             if (i + 1 >= argc) throw std::runtime_error("Option '" + word + "' is missing an argument");
             option->second(argv[++i]);
         } else if (word == "--host-resize") s.host_resize = true;
+        else if (word == "--write-regions") s.write_regions = true;
         else if (!word.empty() && word[0] == '-') throw std::runtime_error("Option '" + word + "' does not exist");
         else if (s.directory.empty()) s.directory = word;
         else throw std::runtime_error("Unexpected argument " + word);
@@ -104,6 +110,27 @@ void echo_per_class(const char* caption, const std::vector<double>& values) {
     std::cout << caption;
     for (size_t k = 0; k < values.size(); ++k) std::cout << " " << k << ":" << values[k];
     std::cout << std::endl;
+}
+
+// ---- --write-regions: the table annonet_infer_regions() leaves, as <image>_result_regions.csv ------------------------------------------
+// One header line, then one line per DETECTED blob in blob-number order.  The header's last field names the downscaling factor the
+// boxes have to be multiplied by to reach the original image; the lines carry the nine fields before it.
+std::string csv_field(const std::string& text) {
+    if (text.find_first_of(",\"\n") == std::string::npos) return text;
+    std::string quoted = "\"";
+    for (const char c : text) { if (c == '"') quoted += '"'; quoted += c; }
+    return quoted + "\"";
+}
+void write_regions_csv(const std::string& path, const std::vector<anh_region>& regions, const std::vector<AnnoClass>& classes, double downscaling) {
+    std::ofstream out(path);
+    out << "class_index,class_name,left,top,right,bottom,area,seeds,peak,downscaling_factor=" << downscaling << "\n";
+    out << std::setprecision(9);   // a float survives the round trip
+    for (const anh_region& r : regions) {
+        if (!r.detected) continue;
+        out << r.label << ',' << csv_field(r.label < classes.size() ? classes[r.label].classlabel : std::string()) << ',' << r.left << ',' << r.top << ','
+            << r.right << ',' << r.bottom << ',' << r.area << ',' << r.seeds << ',' << r.peak << "\n";
+    }
+    if (!out.flush()) throw std::runtime_error("could not write " + path);
 }
 
 // ---- the trained net: annonet.dnn = (anno classes json, downscaling factor, serialized RuntimeNet) ---------------------------------
@@ -245,7 +272,9 @@ int run(const Settings& settings) {
     size_t labelled_pixels = 0;
     InferenceClock clock;
     annonet_infer_temp scratch;
-    const bool resize_on_gpu = trained.downscaling != 1.0 && !settings.host_resize;
+    // --write-regions: the table belongs to the map at the net's resolution, which annonet_infer_regions() computes on an image the readers
+    // have shrunk (the --host-resize route), image by image
+    const bool resize_on_gpu = trained.downscaling != 1.0 && !settings.host_resize && !settings.write_regions;
     {
         ImageReaders readers(files, settings.readers, trained.classes, trained.downscaling, !resize_on_gpu);
         ResultWriters writers(settings.writers, files.size(), trained.classes);
@@ -267,7 +296,7 @@ int run(const Settings& settings) {
         // --image-batch N > 1: up to N consecutive samples of one size wait here and go through annonet_infer_batch() together; a sample
         // of another size flushes them first.  Where the GPU resizes (a factor other than 1 without --host-resize) the samples come at
         // their ORIGINAL size, the groups form on it and go through annonet_infer_scaled_batch().
-        const bool batched = settings.image_batch > 1;
+        const bool batched = settings.image_batch > 1 && !settings.write_regions;
         std::vector<sample_type> pending;
         auto flush = [&] {
             if (pending.empty()) return;
@@ -299,9 +328,11 @@ int run(const Settings& settings) {
 
             const auto t0 = std::chrono::steady_clock::now();
             if (resize_on_gpu) annonet_infer_scaled(trained.net, sample.input_image, trained.downscaling, result.labels, scratch, gains, detection_levels, tiles);
+            else if (settings.write_regions) annonet_infer_regions(trained.net, sample.input_image, result.labels, scratch, gains, detection_levels, tiles);
             else annonet_infer(trained.net, sample.input_image, result.labels, scratch, gains, detection_levels, tiles);
             clock.record(std::chrono::duration_cast<InferenceClock::us>(std::chrono::steady_clock::now() - t0));
             score(sample, resize_on_gpu ? scratch.scaled_result_image : result.labels);
+            if (settings.write_regions) write_regions_csv(sample.image_filenames.image_filename + "_result_regions.csv", scratch.regions, trained.classes, trained.downscaling);
             writers.submit(std::move(result));
         }
         flush();

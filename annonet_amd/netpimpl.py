@@ -5,6 +5,7 @@ annonet_infer() (annonet_infer.h:34-42), set_weights() and tiling::get_tiles, ov
 Method names follow the C++ ones so that tests read like the reference's own host code.  numpy arrays stand in for
 dlib::matrix (row-major, u8 HWC images, u16 label images).
 """
+import atexit
 import ctypes as C
 
 import numpy as np
@@ -573,6 +574,115 @@ def resize_labels_batch(maps, out_w, out_h, prefill=None):
     L = _lib.lib()
     return _through_device(a, (a.shape[0], out_h, out_w), np.uint16, prefill,
                            lambda s, d, st: check(L.anh_resize_labels_batch_device(s, a.shape[0], a.shape[1], a.shape[2], d, out_h, out_w, st)))
+
+
+REGION_DTYPE = np.dtype({"names": ["blob", "label", "detected", "left", "top", "right", "bottom", "first_row", "first_col", "area", "seeds", "peak"],
+                         "formats": ["<u4", "<u2", "<u2", "<i4", "<i4", "<i4", "<i4", "<i4", "<i4", "<i8", "<i8", "<f4"],
+                         "offsets": [0, 4, 6, 8, 12, 16, 20, 24, 28, 32, 40, 48], "itemsize": C.sizeof(_lib.Region)})   # anh_region
+
+_blob_net = None
+
+
+def _net_for_blobs(net):
+    """the handle whose stream the labelling runs on: the caller's, or a smallest net of the module's own (the labelling uses no weights)"""
+    global _blob_net
+    if net is not None:
+        return net
+    if _blob_net is None:
+        _blob_net = RuntimeNet(net_config(1, 3, 3, 0.25, 4, ANH_FP32))
+        atexit.register(_drop_blob_net)   # released while the interpreter and the HIP runtime are still whole
+    return _blob_net
+
+
+def _drop_blob_net():
+    global _blob_net
+    _blob_net = None
+
+
+def _take_regions(L, table, n):
+    """the malloc'd table of a regions call -> numpy structured array (REGION_DTYPE); releases the block"""
+    try:
+        # (a view of the bytes as they came: numpy's copy of a structured array leaves the padding of its rows undefined)
+        return np.frombuffer(bytearray(C.string_at(table, n * REGION_DTYPE.itemsize)), REGION_DTYPE) if n else np.zeros(0, REGION_DTYPE)
+    finally:
+        L.anh_free(table)
+
+
+def label_blobs(label_map, prefill=None, net=None):
+    """The device's connected-blob labelling (anh_label_blobs_device) on a host u16 label map: (u32 blob map, count), count = blobs + 1 as
+    label_connected_blobs returns it.  `prefill`: byte the blob map is filled with before the kernels run (tests: every element must be
+    written)."""
+    a = np.require(label_map, dtype=np.uint16, requirements=["C", "W"])   # (torch wants a writable source)
+    if a.ndim != 2:
+        raise AnnonetHipError(1, "label_blobs: a label map [H,W]")
+    net = _net_for_blobs(net)
+    count = C.c_uint32()
+
+    def launch(s, d, st):
+        import torch
+        torch.cuda.current_stream().synchronize()   # the upload and the prefill ran on torch's stream; the labelling runs on the handle's
+        check(net.L.anh_label_blobs_device(net.h, s, a.shape[0], a.shape[1], d, C.byref(count)))
+    blobs = _through_device(a, a.shape, np.uint32, prefill, launch)
+    return blobs, count.value
+
+
+def regions_device(net, d_labels_ptr, d_blended_ptr, classes, height, width, detection_levels=None, apply_filter=False, d_blobs_ptr=0):
+    """anh_regions_device on resident buffers (device pointers as ints): the region table as a numpy structured array (REGION_DTYPE)."""
+    d = np.ascontiguousarray(detection_levels, dtype=np.float64) if detection_levels is not None else None
+    if d is not None and d.size != classes:
+        raise AnnonetHipError(1, "detection levels need one value per class")
+    table, n = C.POINTER(_lib.Region)(), C.c_size_t()
+    check(net.L.anh_regions_device(net.h, d_labels_ptr, d_blended_ptr, classes, height, width, _ptr(d), 1 if apply_filter else 0, d_blobs_ptr or None,
+                                   C.byref(table), C.byref(n)))
+    return _take_regions(net.L, table, n.value)
+
+
+def regions(label_map, blended, detection_levels=None, apply_filter=False, prefill=None, net=None):
+    """anh_regions_device on host arrays (torch moves the bytes): u16 label map [H,W] and fp32 planes [K,H,W] ->
+    (region table, u32 blob map, the label map as the call leaves it)."""
+    import torch
+    lab = np.require(label_map, dtype=np.uint16, requirements=["C", "W"])
+    planes = np.require(blended, dtype=np.float32, requirements=["C", "W"])
+    if lab.ndim != 2 or planes.ndim != 3 or planes.shape[1:] != lab.shape:
+        raise AnnonetHipError(1, "regions: a label map [H,W] and planes [K,H,W]")
+    net = _net_for_blobs(net)
+    H, W = lab.shape
+    d_lab = torch.from_numpy(lab.view(np.uint8).reshape(-1)).cuda()
+    d_planes = torch.from_numpy(planes).cuda()
+    n = H * W * 4
+    d_blobs = torch.empty(n, dtype=torch.uint8, device="cuda") if prefill is None else torch.full((n,), int(prefill) & 255, dtype=torch.uint8, device="cuda")
+    torch.cuda.current_stream().synchronize()
+    table = regions_device(net, d_lab.data_ptr(), d_planes.data_ptr(), planes.shape[0], H, W, detection_levels, apply_filter, d_blobs.data_ptr())
+    return table, d_blobs.cpu().numpy().view(np.uint32).reshape(H, W), d_lab.cpu().numpy().view(np.uint16).reshape(H, W)
+
+
+def annonet_infer_regions(net, input_image, gains=None, detection_levels=None, tiling_parameters=None, want_blobs=False, want_blended=False):
+    """annonet_infer() plus the region table of its unfiltered label map (anh_infer_regions): returns (label map, table as a numpy
+    structured array of REGION_DTYPE), followed by the u32 blob map and the blended planes when asked for."""
+    img = np.ascontiguousarray(input_image, dtype=np.uint8)
+    if img.ndim == 2:
+        img = img[:, :, None]
+    H, W, c = img.shape
+    if c != net.cfg.in_channels:
+        raise AnnonetHipError(1, "channel count does not match the net input")
+    K = net.cfg.classes
+    res = np.empty((H, W), np.uint16)
+    blobs = np.empty((H, W), np.uint32) if want_blobs else None
+    bl = np.empty((K, H, W), np.float32) if want_blended else None
+    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
+    d = np.ascontiguousarray(detection_levels, dtype=np.float64) if detection_levels is not None else None
+    if g is not None and g.size != K or d is not None and d.size != K:
+        raise AnnonetHipError(1, "gains / detection levels need one value per class")
+    tp = tiling_parameters._c() if tiling_parameters is not None else None
+    table, n = C.POINTER(_lib.Region)(), C.c_size_t()
+    check(net.L.anh_infer_regions(net.h, _ptr(img), H, W, _ptr(g), _ptr(d), C.byref(tp) if tp is not None else None, _ptr(res), _ptr(blobs), _ptr(bl),
+                                  C.byref(table), C.byref(n)))
+    out = [res, _take_regions(net.L, table, n.value)]
+    if want_blobs:
+        out.append(blobs)
+    if want_blended:
+        out.append(bl)
+    return tuple(out)
 
 
 def argmax_device(net, d_blended_ptr, height, width, row0, row1, d_labels_ptr, gains=None):

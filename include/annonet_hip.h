@@ -227,6 +227,42 @@ int anh_infer_scaled_batch(anh_runtime* h, const uint8_t* const* images_hwc, int
 int anh_infer_scaled_batch_device(anh_runtime* h, const uint8_t* d_images_hwc, int n, int height, int width, double downscaling_factor,
                                   const double* gains, const anh_tiling_params* tiling,
                                   uint16_t* d_results, uint16_t* d_scaled_labels, float* d_blended);
+/* ---- connected blobs: what annonet_infer() leaves in annonet_infer_temp::connected_blobs / detection_seeds (annonet_infer.cpp:194-223) ----
+ * A blob is an 8-connected set of pixels of EQUAL non-zero label (0 = background; every other value, ANH_LABEL_IGNORE included, is a
+ * label like the rest).  Blobs are numbered 1, 2, ... in raster order of their first pixel, the numbering annonet_amd/host/annonet_host.h:
+ * label_connected_blobs restates for dlib's routine [UPSTREAM-UNVERIFIED].  Labelling runs on the device (block-based union-find); the maps
+ * are limited to height * width < 2^31 pixels (ANH_ERR_INVALID beyond).  All work runs on the handle's stream (replica 0 of a handle with
+ * several); the calls synchronise it, because the blob count comes back to the host.
+ * One row of the region table, by integer atomics only — the same bits on every run: */
+typedef struct {
+    uint32_t blob;                   /* the blob's number, 1-based: row i of a table describes blob i + 1 */
+    uint16_t label;
+    uint16_t detected;               /* a positive detection level was given: seeds > 0; none: 1 */
+    int32_t left, top, right, bottom; /* bounding box, inclusive */
+    int32_t first_row, first_col;    /* the blob's first pixel in raster order */
+    int64_t area, seeds;             /* pixels; detection seeds attributed to the blob (annonet_infer.cpp:199-213,222) */
+    float peak;                      /* largest blended[label][p] - blended[0][p] over the blob's pixels, subtracted in float; NaN never wins;
+                                        -inf for a label >= classes (and where every margin is NaN) */
+} anh_region;
+/* d_labels [height][width] u16 -> d_blobs [height][width] u32 (0 on background, else the blob's number);
+ * *count = "labels including the background one" = blobs + 1, as label_connected_blobs returns it */
+int anh_label_blobs_device(anh_runtime* h, const uint16_t* d_labels, int height, int width, uint32_t* d_blobs, uint32_t* count);
+/* The table of every blob of the label map AS IT COMES IN, in number order: *regions (malloc'd, release with anh_free) holds *n_regions
+ * rows.  d_blended: `classes` planes [height][width].  detection_levels: `classes` host doubles or NULL; a pixel is a seed of its blob
+ * where blended[label] - blended[0] > levels[label] - levels[0], as the detection-level filter of anh_infer decides it
+ * (ANH_DET_SEED_REFERENCE_ORDER=1: the reference's transposed lookup, as there).  When no level is positive (NULL or all zero) the levels
+ * count as zeros for `seeds`, nothing is ever removed and detected = 1 in every row.  apply_filter != 0 with a positive level: ONE launch
+ * afterwards sets d_labels to 0 on every blob without a seed — the map anh_infer's filter leaves; the blob map keeps the numbers of the
+ * removed blobs.  d_blobs: NULL, or height * width u32 that receive the blob map.  Everything but the table is reserved before the
+ * first kernel; the table is reserved once the count is known, and if that fails the call returns ANH_ERR_OOM and the handle stays usable. */
+int anh_regions_device(anh_runtime* h, uint16_t* d_labels, const float* d_blended, int classes, int height, int width,
+                       const double* detection_levels, int apply_filter, uint32_t* d_blobs, anh_region** regions, size_t* n_regions);
+/* anh_infer plus the region table of its UNFILTERED label map (annonet_infer.cpp:217 labels before :229-238 filter): result_labels and
+ * blended_out are bit-identical to what anh_infer returns for the same arguments on one device.  blobs: NULL, or height * width u32 on
+ * the host. */
+int anh_infer_regions(anh_runtime* h, const uint8_t* image_hwc, int height, int width,
+                      const double* gains, const double* detection_levels, const anh_tiling_params* tiling,
+                      uint16_t* result_labels, uint32_t* blobs, float* blended_out, anh_region** regions, size_t* n_regions);
 /* label rows [row0, row1) of device-resident blended planes (find_label, annonet_infer.cpp:170-185): the second half of a
    sharded annonet_infer(), run after the ranks have exchanged the plane sums of their overlapping tiles */
 int anh_argmax_device(anh_runtime* h, const float* d_blended, int height, int width, int row0, int row1, const double* gains, uint16_t* d_result);

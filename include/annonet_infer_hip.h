@@ -30,6 +30,11 @@ struct annonet_infer_temp {  // annonet_infer.h:26-32; the GPU path keeps its sc
     bool keep_blended_output = annonet_hip_keep_blended_default();
     dlib::matrix<uint16_t> scaled_result_image;       // annonet_infer_scaled: the label map at the net's resolution, filled on every scaled call
     std::vector<dlib::matrix<uint16_t>> scaled_result_images;   // annonet_infer_scaled_batch: one such map per image, filled on every call
+    // annonet_infer_regions: one row per connected blob of the UNFILTERED label map, in blob-number order (anh_region, annonet_hip.h);
+    // connected_blobs (the reference fills it on every call, annonet_infer.cpp:217) travels back only when keep_connected_blobs is set.
+    // detection_seeds stays empty: it can be as long as the image, and regions[i].seeds carries the count per blob.
+    std::vector<anh_region> regions;
+    bool keep_connected_blobs = false;
 };
 
 inline void annonet_infer(NetPimpl::RuntimeNet& net, const NetPimpl::input_type& input_image, dlib::matrix<uint16_t>& result_image,
@@ -48,6 +53,42 @@ inline void annonet_infer(NetPimpl::RuntimeNet& net, const NetPimpl::input_type&
     NetPimpl::check(anh_infer(net.handle(), reinterpret_cast<const uint8_t*>(&*input_image.begin()), H, W, gains.empty() ? nullptr : gains.data(),
                               detection_levels.empty() ? nullptr : detection_levels.data(), &tp, &*result_image.begin(),
                               temp.keep_blended_output ? planes.data() : nullptr));
+    if (temp.keep_blended_output) {
+        temp.blended_output.resize(K);
+        for (int k = 0; k < K; ++k) {
+            temp.blended_output[k].set_size(H, W);
+            std::copy(planes.begin() + (size_t)k * H * W, planes.begin() + (size_t)(k + 1) * H * W, temp.blended_output[k].begin());
+        }
+    }
+}
+
+// annonet_infer() that also leaves what the reference computes on the way to its detection-level filter (annonet_infer.cpp:194-223): the
+// connected blobs of the label map BEFORE the filter and, per blob, class, bounding box, area, seed count and peak margin over "clean"
+// (anh_infer_regions; labelled on the device).  result_image is bit-identical to annonet_infer()'s on one device.  Always fills
+// temp.regions; temp.connected_blobs when temp.keep_connected_blobs is set; temp.blended_output keeps its keep_blended_output rule.
+inline void annonet_infer_regions(NetPimpl::RuntimeNet& net, const NetPimpl::input_type& input_image, dlib::matrix<uint16_t>& result_image,
+                                  annonet_infer_temp& temp, const std::vector<double>& gains = std::vector<double>(),
+                                  const std::vector<double>& detection_levels = std::vector<double>(),
+                                  const tiling::parameters& tiling_parameters = tiling::parameters()) {
+    anh_net_config cfg;
+    NetPimpl::check(anh_runtime_config(net.handle(), &cfg));
+    const int K = cfg.classes, H = (int)input_image.nr(), W = (int)input_image.nc();
+    if (!gains.empty() && (int)gains.size() != K) throw std::runtime_error("annonet_infer_regions: one gain per class expected");
+    if (!detection_levels.empty() && (int)detection_levels.size() != K) throw std::runtime_error("annonet_infer_regions: one detection level per class expected");
+    result_image.set_size(H, W);
+    std::vector<float> planes;
+    if (temp.keep_blended_output) planes.resize((size_t)K * H * W);
+    if (temp.keep_connected_blobs) temp.connected_blobs.set_size(H, W);
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "connected_blobs receives the u32 blob map as it is");
+    anh_tiling_params tp{tiling_parameters.max_tile_width, tiling_parameters.max_tile_height, tiling_parameters.overlap_x, tiling_parameters.overlap_y};
+    anh_region* table = nullptr;
+    size_t rows = 0;
+    NetPimpl::check(anh_infer_regions(net.handle(), reinterpret_cast<const uint8_t*>(&*input_image.begin()), H, W, gains.empty() ? nullptr : gains.data(),
+                                      detection_levels.empty() ? nullptr : detection_levels.data(), &tp, &*result_image.begin(),
+                                      temp.keep_connected_blobs ? reinterpret_cast<uint32_t*>(&*temp.connected_blobs.begin()) : nullptr,
+                                      temp.keep_blended_output ? planes.data() : nullptr, &table, &rows));
+    try { temp.regions.assign(table, table + rows); } catch (...) { anh_free(table); throw; }
+    anh_free(table);
     if (temp.keep_blended_output) {
         temp.blended_output.resize(K);
         for (int k = 0; k < K; ++k) {
