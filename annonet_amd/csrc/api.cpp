@@ -288,19 +288,21 @@ bool detection_requested(const double* detection_levels, int K) {
 }
 // detection-level filter (annonet_infer.cpp:187-239), on resident planes [K][h][w] and their label map of h x w.
 // Seeds are looked up at (row, col): the reference stores (r, c) but reads (point.y(), point.x()) — transposed (:210 vs :222); see DESIGN.md.
+// Its scratch, e.stage_out of detection_scratch_bytes, is the caller's to reserve (with the rest, before its first kernel).
 size_t detection_scratch_bytes(size_t plane, int K) { return plane + (size_t)K * sizeof(double) + 64; }   // flags, levels, the change counter
 void apply_detection_levels(Engine& e, const double* levels, int K, int h, int w, const float* d_blended, uint16_t* d_labels) {
     const size_t plane = (size_t)h * w;
-    e.stage_out.reserve(detection_scratch_bytes(plane, K));
     uint8_t* flags = e.stage_out.as<uint8_t>();
     double* d_det = reinterpret_cast<double*>(flags + ((plane + 15) / 16) * 16);
     int* d_changed = reinterpret_cast<int*>(d_det + K);
     HIP_CHECK(hipMemcpyAsync(d_det, levels, (size_t)K * sizeof(double), hipMemcpyHostToDevice, e.stream));
     run_detection_filter(d_blended, d_labels, K, h, w, d_det, flags, d_changed, e.stream);
 }
-// ... on the handle's stage buffers (anh_infer, anh_infer_scaled)
-void apply_detection_levels(Engine& e, const double* levels, int K, int h, int w) {
-    apply_detection_levels(e, levels, K, h, w, e.stage_blended.as<float>(), e.stage_result.as<uint16_t>());
+// stage_image / stage_result for n images of `plane` pixels, and stage_blended for their class planes where a path blends into them
+void reserve_stage(Engine& e, size_t n, size_t plane, bool planes = true) {
+    e.stage_image.reserve(n * plane * e.spec.cfg.in_channels);
+    if (planes) e.stage_blended.reserve(n * plane * e.spec.cfg.classes * 4);
+    e.stage_result.reserve(n * plane * 2);
 }
 }  // namespace
 
@@ -619,18 +621,64 @@ void infer_streamed(anh_runtime* h, const uint8_t* image, int H, int W, const do
 }  // namespace
 
 namespace {
-// annonet_infer() on a handle with several replicas (anh_set_devices): the tile list is split into contiguous row-major chunks
+// ---- one host-buffer inference call ----
+// What anh_infer, anh_infer_regions, anh_infer_batch, anh_infer_scaled and anh_infer_scaled_batch ask for, as ONE value: the entry
+// points check their arguments and fill it, run_host_infer decides who serves it, run_share is the body that runs it.
+struct HostInfer {
+    enum class Tail { none, filter, regions };
+    const uint8_t* const* images = nullptr;   // n images of H x W, as the caller holds them
+    int n = 1, H = 0, W = 0;
+    bool batch = false;        // a batch form: the forward is infer_batch_device (a single-image form keeps infer_device's launches, engine.hip)
+    double factor = 1.0;       // 1.0: no resize; else the images are shrunk to h x w, the net's resolution, and the maps blown up again
+    int h = 0, w = 0;
+    const double* gains = nullptr;
+    const double* levels = nullptr;
+    std::vector<anh_tile> tiles;   // at the net's resolution
+    uint16_t* const* results = nullptr;   // per image: the map of H x W, ...
+    uint16_t* const* scaled = nullptr;    // ... the map of h x w and the planes [K][h][w]; either list and any entry may be null
+    float* const* planes = nullptr;
+    Tail tail = Tail::none;    // after the forward, at the net's resolution: the detection-level filter (some level is positive), or the region table
+    uint32_t* blobs = nullptr;            // Tail::regions (one image): the blob map (may be null), the malloc'd table
+    anh_region** regions = nullptr;
+    size_t* n_regions = nullptr;
+
+    bool resized() const { return factor != 1.0; }
+    uint16_t* scaled_of(int i) const { return scaled ? scaled[i] : nullptr; }
+    float* planes_of(int i) const { return planes ? planes[i] : nullptr; }
+    HostInfer single(int i) const {   // image i of a batch as the single-image call
+        HostInfer c = *this;
+        c.images += i; c.results += i;
+        if (scaled) c.scaled += i;
+        if (planes) c.planes += i;
+        c.n = 1; c.batch = false;
+        return c;
+    }
+    // from an entry point's (checked) arguments; sh x sw: the net's resolution.  Negative detection levels are refused here, before anything is enqueued.
+    HostInfer(anh_runtime* rt, const uint8_t* const* images, int n, bool batch, int H, int W, double factor, int sh, int sw, const double* gains, const double* levels,
+              const anh_tiling_params* tiling, uint16_t* const* results, uint16_t* const* scaled, float* const* planes)
+        : images(images), n(n), H(H), W(W), batch(batch), factor(factor), h(sh), w(sw), gains(gains), levels(levels), tiles(tiles_for(tiling, sw, sh)),
+          results(results), scaled(scaled), planes(planes),
+          tail(detection_requested(levels, rt->reps.engine(0).spec.cfg.classes) ? Tail::filter : Tail::none) {}
+};
+
+// A single image on a handle with several replicas (anh_set_devices): the tile list is split into contiguous row-major chunks
 // (tiles are independent, annonet_infer.cpp:46-165, except for the additive blended_output), every replica blends its chunk
 // into planes of its own, ONE all-reduce sums the planes inside the rectangles where tiles of different replicas overlap
 // (strips one receptive field wide), every replica labels the rows its tiles cover, and the host label map is assembled tile
 // by tile from the owner of each tile (in an overlap both owners hold the same sums, hence the same labels).
-// `original` (anh_infer_scaled): the image comes at its original size OH x OW; every replica uploads it and shrinks it to H x W itself
-// (the shrunk image is integer-valued and identical everywhere), `image` is unused.
-void infer_multi(anh_runtime* h, const uint8_t* image, int H, int W, const double* gains, const std::vector<anh_tile>& tiles, uint16_t* result, float* blended_out,
-                 const uint8_t* original = nullptr, int OH = 0, int OW = 0) {
+// A resized call: every replica uploads the original image and shrinks it itself (the shrunk image is integer-valued and identical
+// everywhere); the map assembled on the host is the one at the net's resolution, and replica 0 blows it up.
+void infer_multi(anh_runtime* h, const HostInfer& c) {
     const size_t R = h->reps.size();
     const int K = h->reps.engine(0).spec.cfg.classes, C = h->reps.engine(0).spec.cfg.in_channels;
-    const size_t plane = (size_t)H * W;
+    const int H = c.h, W = c.w;
+    const size_t plane = (size_t)H * W, full = (size_t)c.H * c.W;
+    const double* gains = c.gains;
+    const std::vector<anh_tile>& tiles = c.tiles;
+    float* blended_out = c.planes_of(0);
+    std::vector<uint16_t> merged_own;
+    uint16_t* result = !c.resized() ? c.results[0] : c.scaled_of(0);
+    if (!result) { merged_own.resize(plane); result = merged_own.data(); }
     const RectTable table = make_rect_table(cross_replica_overlaps(tiles, (int)R, W, H));
     const int64_t total = table.total();
     std::vector<float*> packed(R, nullptr);
@@ -638,15 +686,14 @@ void infer_multi(anh_runtime* h, const uint8_t* image, int H, int W, const doubl
     std::vector<int64_t> lo(R), hi(R);
     h->reps.each([&](size_t r, Engine& e) {
         shard_range((int64_t)tiles.size(), (int)R, (int)r, lo[r], hi[r]);
-        e.stage_image.reserve(plane * C);
-        e.stage_blended.reserve(plane * K * 4);
-        e.stage_result.reserve(plane * 2);
-        if (original) {
-            e.stage_original.reserve((size_t)OH * OW * C);
-            HIP_CHECK(hipMemcpyAsync(e.stage_original.p, original, (size_t)OH * OW * C, hipMemcpyHostToDevice, e.stream));
-            e.resize_image(e.stage_original.as<uint8_t>(), OH, OW, e.stage_image.as<uint8_t>(), H, W);
+        reserve_stage(e, 1, plane);
+        if (c.resized()) {
+            e.stage_original.reserve(full * C);
+            if (r == 0) e.stage_upsampled.reserve(full * 2);
+            HIP_CHECK(hipMemcpyAsync(e.stage_original.p, c.images[0], full * C, hipMemcpyHostToDevice, e.stream));
+            e.resize_image(e.stage_original.as<uint8_t>(), c.H, c.W, e.stage_image.as<uint8_t>(), H, W);
         } else
-            HIP_CHECK(hipMemcpyAsync(e.stage_image.p, image, plane * C, hipMemcpyHostToDevice, e.stream));
+            HIP_CHECK(hipMemcpyAsync(e.stage_image.p, c.images[0], plane * C, hipMemcpyHostToDevice, e.stream));
         const std::vector<anh_tile> mine(tiles.begin() + lo[r], tiles.begin() + hi[r]);
         e.infer_device(e.stage_image.as<uint8_t>(), H, W, gains, mine, nullptr, e.stage_blended.as<float>());
         streams[r] = e.stream;
@@ -688,6 +735,95 @@ void infer_multi(anh_runtime* h, const uint8_t* image, int H, int W, const doubl
         }
     });
     h->reps.for_all([](size_t, Engine& e) { e.synchronize(); });
+    if (!c.resized()) return;
+    Engine& e = h->reps.engine(0);   // (the caller holds replica 0's device)
+    HIP_CHECK(hipMemcpyAsync(e.stage_result.p, result, plane * 2, hipMemcpyHostToDevice, e.stream));
+    e.resize_labels(e.stage_result.as<uint16_t>(), H, W, e.stage_upsampled.as<uint16_t>(), c.H, c.W);
+    HIP_CHECK(hipMemcpyAsync(c.results[0], e.stage_upsampled.p, full * 2, hipMemcpyDeviceToHost, e.stream));
+    e.synchronize();
+}
+
+// THE body of a host-buffer call: images [lo, hi) of `c` on one engine, under its device and on its stream.  Reserve everything the
+// share uses (a share that cannot fit fails with ANH_ERR_OOM before its first kernel), upload, shrink, forward, tail, blow up,
+// download, synchronise.
+void run_share(Engine& e, const HostInfer& c, int lo, int hi) {
+    using Tail = HostInfer::Tail;
+    const int m = hi - lo, K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
+    const size_t plane = (size_t)c.h * c.w, full = (size_t)c.H * c.W;
+    bool planes = !c.batch || c.tail != Tail::none;   // infer_device blends into planes whoever wants them; both tails read them
+    for (int i = lo; i < hi; ++i) planes = planes || c.planes_of(i) != nullptr;
+    reserve_stage(e, (size_t)m, plane, planes);
+    if (c.resized()) { e.stage_original.reserve((size_t)m * full * C); e.stage_upsampled.reserve((size_t)m * full * 2); }
+    if (c.tail == Tail::filter) e.stage_out.reserve(detection_scratch_bytes(plane, K));
+    if (c.tail == Tail::regions) (void)e.reserve_blobs(c.h, c.w, K, true);
+    if (c.batch) e.reserve_infer_batch(m, c.h, c.w, c.tiles, planes);   // the forward's own, ahead of the shrink
+    uint8_t* d_image = e.stage_image.as<uint8_t>();
+    float* d_planes = planes ? e.stage_blended.as<float>() : nullptr;
+    uint16_t* d_labels = e.stage_result.as<uint16_t>();
+    const uint16_t* d_results = d_labels;   // the maps of H x W
+    uint8_t* d_upload = c.resized() ? e.stage_original.as<uint8_t>() : d_image;
+    for (int i = 0; i < m; ++i) HIP_CHECK(hipMemcpyAsync(d_upload + (size_t)i * full * C, c.images[lo + i], full * C, hipMemcpyHostToDevice, e.stream));
+    if (c.resized()) e.resize_image_batch(d_upload, m, c.H, c.W, d_image, c.h, c.w);
+    if (c.batch) e.infer_batch_device(d_image, m, c.h, c.w, c.gains, c.tiles, d_labels, d_planes);
+    else e.infer_device(d_image, c.h, c.w, c.gains, c.tiles, d_labels, d_planes, /*whole_image=*/true);
+    // the tails run at the net's resolution, as the reference runs its filter before resize_label_image
+    std::unique_ptr<anh_region, decltype(&std::free)> table(nullptr, &std::free);
+    size_t rows = 0;
+    const uint32_t* d_blobs = nullptr;
+    for (int i = 0; i < m; ++i) {
+        if (c.tail == Tail::filter) apply_detection_levels(e, c.levels, K, c.h, c.w, d_planes + (size_t)i * K * plane, d_labels + (size_t)i * plane);
+        if (c.tail == Tail::regions) {   // (one image: the call has one table)
+            anh_region* t = nullptr;
+            d_blobs = e.regions(d_labels, d_planes, K, c.h, c.w, c.levels, /*filter=*/true, nullptr, &t, &rows);
+            table.reset(t);
+        }
+    }
+    if (c.resized()) {
+        e.resize_labels_batch(d_labels, m, c.h, c.w, e.stage_upsampled.as<uint16_t>(), c.H, c.W);
+        d_results = e.stage_upsampled.as<uint16_t>();
+    }
+    for (int i = 0; i < m; ++i) {
+        HIP_CHECK(hipMemcpyAsync(c.results[lo + i], d_results + (size_t)i * full, full * 2, hipMemcpyDeviceToHost, e.stream));
+        if (c.resized() && c.scaled_of(lo + i)) HIP_CHECK(hipMemcpyAsync(c.scaled_of(lo + i), d_labels + (size_t)i * plane, plane * 2, hipMemcpyDeviceToHost, e.stream));
+        if (d_blobs && c.blobs) HIP_CHECK(hipMemcpyAsync(c.blobs, d_blobs, plane * 4, hipMemcpyDeviceToHost, e.stream));
+        if (c.planes_of(lo + i)) HIP_CHECK(hipMemcpyAsync(c.planes_of(lo + i), d_planes + (size_t)i * K * plane, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
+    }
+    e.synchronize();
+    if (c.tail == Tail::regions) { *c.regions = table.release(); *c.n_regions = rows; }
+}
+
+// A single image, on replica 0 unless its tiles can be shared out.
+void run_single(anh_runtime* h, const HostInfer& c) {
+    DeviceScope scope(h->reps.device_of(0));
+    Engine& e = h->reps.engine(0);
+    // several replicas: shard the tile list (the filter and the region table walk connected blobs of the WHOLE label map: they run on
+    // replica 0 alone, as does an image with fewer tiles than replicas would gain nothing)
+    if (h->reps.size() > 1 && c.tail == HostInfer::Tail::none && c.tiles.size() >= 2) { infer_multi(h, c); return; }
+    static const bool streamed = read_switch("ANH_INFER_STREAMED", true);
+    if (streamed && !c.resized() && c.tail == HostInfer::Tail::none && !c.planes_of(0)) {
+        reserve_stage(e, 1, (size_t)c.h * c.w);
+        infer_streamed(h, c.images[0], c.h, c.w, c.gains, c.tiles, c.results[0]);
+        return;
+    }
+    run_share(e, c, 0, 1);
+}
+
+// Who serves a host-buffer call.  A single-image form: run_single.  A batch form: every replica takes a contiguous share of the images
+// (an image is computed wholly on one replica, so nothing is exchanged); fewer images than replicas are served image by image, as
+// the single-image form serves them.  Factor 1.0 is exactly the unscaled call (the host's bilinear returns early at scale 1, nearest
+// neighbour at equal size is the identity): the map at the net's resolution is then a copy of the result.
+void run_host_infer(anh_runtime* h, const HostInfer& c) {
+    const size_t R = h->reps.size();
+    if (!c.batch) run_single(h, c);
+    else if ((size_t)c.n < R) for (int i = 0; i < c.n; ++i) run_single(h, c.single(i));
+    else
+        h->reps.each([&](size_t r, Engine& e) {
+            int64_t lo = 0, hi = 0;
+            shard_range((int64_t)c.n, (int)R, (int)r, lo, hi);
+            if (hi > lo) run_share(e, c, (int)lo, (int)hi);
+        });
+    if (!c.resized())
+        for (int i = 0; i < c.n; ++i) if (c.scaled_of(i)) std::memcpy(c.scaled_of(i), c.results[i], (size_t)c.H * c.W * 2);
 }
 }  // namespace
 
@@ -696,26 +832,7 @@ int anh_infer(anh_runtime* h, const uint8_t* image, int height, int width, const
     return guarded([&] {
         ANH_REQUIRE(h && image && result, "null argument");
         ANH_REQUIRE(height >= 1 && width >= 1, "empty image");
-        DeviceScope scope(h->reps.device_of(0));
-        Engine& e = h->reps.engine(0);
-        const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
-        const size_t plane = (size_t)height * width;
-        std::vector<anh_tile> tiles = tiles_for(tiling, width, height);
-        e.stage_image.reserve(plane * C);
-        e.stage_blended.reserve(plane * K * 4);
-        e.stage_result.reserve(plane * 2);
-        const bool use_det = detection_requested(detection_levels, K);
-        // several replicas: shard the tile list (the detection-level filter walks connected blobs of the WHOLE label map: it runs on
-        // replica 0 alone, as does an image with fewer tiles than replicas would gain nothing)
-        if (h->reps.size() > 1 && !use_det && tiles.size() >= 2) { infer_multi(h, image, height, width, gains, tiles, result, blended_out); return; }
-        static const bool streamed = read_switch("ANH_INFER_STREAMED", true);
-        if (streamed && !use_det && !blended_out) { infer_streamed(h, image, height, width, gains, tiles, result); return; }
-        HIP_CHECK(hipMemcpyAsync(e.stage_image.p, image, plane * C, hipMemcpyHostToDevice, e.stream));
-        e.infer_device(e.stage_image.as<uint8_t>(), height, width, gains, tiles, e.stage_result.as<uint16_t>(), e.stage_blended.as<float>(), /*whole_image=*/true);
-        if (use_det) apply_detection_levels(e, detection_levels, K, height, width);
-        HIP_CHECK(hipMemcpyAsync(result, e.stage_result.p, plane * 2, hipMemcpyDeviceToHost, e.stream));
-        if (blended_out) HIP_CHECK(hipMemcpyAsync(blended_out, e.stage_blended.p, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
-        e.synchronize();
+        run_host_infer(h, HostInfer(h, &image, 1, false, height, width, 1.0, height, width, gains, detection_levels, tiling, &result, nullptr, &blended_out));
     });
 }
 
@@ -752,29 +869,10 @@ int anh_infer_regions(anh_runtime* h, const uint8_t* image, int height, int widt
     return guarded([&] {
         require_blob_map_size(height, width);
         ANH_REQUIRE(h && image && result && regions && n_regions, "null argument");
-        DeviceScope scope(h->reps.device_of(0));
-        Engine& e = h->reps.engine(0);   // the blobs are those of the WHOLE label map: replica 0 alone, as anh_infer's filter
-        const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
-        const size_t plane = (size_t)height * width;
-        std::vector<anh_tile> tiles = tiles_for(tiling, width, height);
-        (void)detection_requested(detection_levels, K);   // negative levels are refused before anything is enqueued
-        e.stage_image.reserve(plane * C);
-        e.stage_blended.reserve(plane * K * 4);
-        e.stage_result.reserve(plane * 2);
-        (void)e.reserve_blobs(height, width, K, true);
-        HIP_CHECK(hipMemcpyAsync(e.stage_image.p, image, plane * C, hipMemcpyHostToDevice, e.stream));
-        e.infer_device(e.stage_image.as<uint8_t>(), height, width, gains, tiles, e.stage_result.as<uint16_t>(), e.stage_blended.as<float>(), /*whole_image=*/true);
-        anh_region* table = nullptr;
-        size_t rows = 0;
-        const uint32_t* d_blobs = e.regions(e.stage_result.as<uint16_t>(), e.stage_blended.as<float>(), K, height, width, detection_levels, /*filter=*/true, nullptr, &table, &rows);
-        try {
-            HIP_CHECK(hipMemcpyAsync(result, e.stage_result.p, plane * 2, hipMemcpyDeviceToHost, e.stream));
-            if (blobs) HIP_CHECK(hipMemcpyAsync(blobs, d_blobs, plane * 4, hipMemcpyDeviceToHost, e.stream));
-            if (blended_out) HIP_CHECK(hipMemcpyAsync(blended_out, e.stage_blended.p, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
-            e.synchronize();
-        } catch (...) { std::free(table); throw; }
-        *regions = table;
-        *n_regions = rows;
+        HostInfer c(h, &image, 1, false, height, width, 1.0, height, width, gains, detection_levels, tiling, &result, nullptr, &blended_out);
+        c.tail = HostInfer::Tail::regions;   // the blobs are those of the WHOLE label map: replica 0 alone, as anh_infer's filter
+        c.blobs = blobs; c.regions = regions; c.n_regions = n_regions;
+        run_host_infer(h, c);
     });
 }
 
@@ -798,43 +896,7 @@ int anh_infer_batch(anh_runtime* h, const uint8_t* const* images, int n, int hei
         ANH_REQUIRE(h, "null handle");
         ANH_REQUIRE(height >= 1 && width >= 1, "empty image");
         for (int i = 0; i < n; ++i) ANH_REQUIRE(images[i] && results[i], "infer_batch: null image or result");
-        const size_t R = h->reps.size();
-        if ((size_t)n < R) {   // fewer images than replicas: image by image, as anh_infer serves them
-            for (int i = 0; i < n; ++i) {
-                const int rc = anh_infer(h, images[i], height, width, gains, detection_levels, tiling, results[i], blended_out ? blended_out[i] : nullptr);
-                if (rc != ANH_OK) fail(rc, g_error);
-            }
-            return;
-        }
-        const int K = h->reps.engine(0).spec.cfg.classes, C = h->reps.engine(0).spec.cfg.in_channels;
-        const size_t plane = (size_t)height * width;
-        const std::vector<anh_tile> tiles = tiles_for(tiling, width, height);
-        const bool use_det = detection_requested(detection_levels, K);
-        // every replica takes a contiguous share of the images; an image is computed wholly on one replica, so nothing is exchanged
-        h->reps.each([&](size_t r, Engine& e) {
-            int64_t lo = 0, hi = 0;
-            shard_range((int64_t)n, (int)R, (int)r, lo, hi);
-            const int m = (int)(hi - lo);
-            if (m <= 0) return;
-            bool planes = use_det;   // the filter reads the planes
-            if (blended_out) for (int64_t i = lo; i < hi; ++i) planes = planes || blended_out[i] != nullptr;
-            e.stage_image.reserve((size_t)m * plane * C);
-            e.stage_result.reserve((size_t)m * plane * 2);
-            if (planes) e.stage_blended.reserve((size_t)m * plane * K * 4);
-            if (use_det) e.stage_out.reserve(detection_scratch_bytes(plane, K));   // (the filter's scratch: reserved with the rest, before the first kernel)
-            for (int i = 0; i < m; ++i)
-                HIP_CHECK(hipMemcpyAsync(e.stage_image.as<uint8_t>() + (size_t)i * plane * C, images[lo + i], plane * C, hipMemcpyHostToDevice, e.stream));
-            float* d_planes = planes ? e.stage_blended.as<float>() : nullptr;
-            uint16_t* d_labels = e.stage_result.as<uint16_t>();
-            e.infer_batch_device(e.stage_image.as<uint8_t>(), m, height, width, gains, tiles, d_labels, d_planes);
-            for (int i = 0; i < m; ++i) {
-                if (use_det) apply_detection_levels(e, detection_levels, K, height, width, d_planes + (size_t)i * K * plane, d_labels + (size_t)i * plane);
-                HIP_CHECK(hipMemcpyAsync(results[lo + i], d_labels + (size_t)i * plane, plane * 2, hipMemcpyDeviceToHost, e.stream));
-                if (blended_out && blended_out[lo + i])
-                    HIP_CHECK(hipMemcpyAsync(blended_out[lo + i], d_planes + (size_t)i * K * plane, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
-            }
-            e.synchronize();
-        });
+        run_host_infer(h, HostInfer(h, images, n, true, height, width, 1.0, height, width, gains, detection_levels, tiling, results, nullptr, blended_out));
     });
 }
 
@@ -880,6 +942,10 @@ void scaled_dims_checked(int height, int width, double factor, int& sh, int& sw)
     ANH_REQUIRE(nr <= 32768 && nc <= 32768, "the downscaling factor enlarges the image beyond 32768 pixels per side");
     sh = (int)nr; sw = (int)nc;
 }
+void require_resize_sides(const char* what, int src_h, int src_w, int dst_h, int dst_w) {
+    ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1 && src_h <= 32768 && src_w <= 32768 && dst_h <= 32768 && dst_w <= 32768,
+                std::string(what) + ": sides must be within 1..32768");
+}
 }  // namespace
 
 int anh_scaled_dims(int height, int width, double downscaling_factor, int* scaled_height, int* scaled_width) {
@@ -892,7 +958,7 @@ int anh_scaled_dims(int height, int width, double downscaling_factor, int* scale
 int anh_resize_image_device(const uint8_t* d_src, int channels, int src_h, int src_w, uint8_t* d_dst, int dst_h, int dst_w, void* hip_stream) {
     return guarded([&] {
         ANH_REQUIRE(d_src && d_dst, "null argument");
-        ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1 && src_h <= 32768 && src_w <= 32768 && dst_h <= 32768 && dst_w <= 32768, "resize_image: sides must be within 1..32768");
+        require_resize_sides("resize_image", src_h, src_w, dst_h, dst_w);
         launch_resize_image_bilinear(d_src, channels, src_h, src_w, d_dst, dst_h, dst_w, (hipStream_t)hip_stream);
     });
 }
@@ -900,33 +966,49 @@ int anh_resize_image_device(const uint8_t* d_src, int channels, int src_h, int s
 int anh_resize_labels_device(const uint16_t* d_src, int src_h, int src_w, uint16_t* d_dst, int dst_h, int dst_w, void* hip_stream) {
     return guarded([&] {
         ANH_REQUIRE(d_src && d_dst, "null argument");
-        ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1 && src_h <= 32768 && src_w <= 32768 && dst_h <= 32768 && dst_w <= 32768, "resize_labels: sides must be within 1..32768");
+        require_resize_sides("resize_labels", src_h, src_w, dst_h, dst_w);
         launch_resize_labels_nearest(d_src, src_h, src_w, d_dst, dst_h, dst_w, (hipStream_t)hip_stream);
     });
 }
+
+namespace {
+// anh_infer_scaled_device (batch false, n = 1: the forward stays infer_device) and anh_infer_scaled_batch_device on resident buffers:
+// enqueued on the handle's stream, not synchronised
+void infer_scaled_on_device(anh_runtime* h, bool batch, const uint8_t* d_images, int n, int height, int width, double downscaling_factor, const double* gains,
+                            const anh_tiling_params* tiling, uint16_t* d_results, uint16_t* d_scaled_labels, float* d_blended) {
+    int sh = 0, sw = 0;
+    scaled_dims_checked(height, width, downscaling_factor, sh, sw);
+    DeviceScope scope(h->reps.device_of(0));
+    Engine& e = h->reps.engine(0);
+    const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
+    const size_t plane = (size_t)sh * sw;
+    const std::vector<anh_tile> tiles = tiles_for(tiling, sw, sh);
+    if (!batch && !d_blended) { e.stage_blended.reserve(plane * K * 4); d_blended = e.stage_blended.as<float>(); }   // infer_device blends into planes
+    auto forward = [&](const uint8_t* d_src, uint16_t* d_labels) {
+        if (batch) e.infer_batch_device(d_src, n, sh, sw, gains, tiles, d_labels, d_blended);
+        else e.infer_device(d_src, sh, sw, gains, tiles, d_labels, d_blended, /*whole_image=*/true);
+    };
+    if (downscaling_factor == 1.0) {   // the host's bilinear returns early at scale 1, nearest neighbour at equal size is the identity
+        forward(d_images, d_results);
+        if (d_scaled_labels) HIP_CHECK(hipMemcpyAsync(d_scaled_labels, d_results, (size_t)n * plane * 2, hipMemcpyDeviceToDevice, e.stream));
+        return;
+    }
+    // reserved before the first kernel; infer_batch_device reserves its own (planes, logits) before its first kernel and writes nothing
+    // the shrink does not own, so a batch that cannot fit has only shrunk images into a stage buffer
+    e.stage_image.reserve((size_t)n * plane * C);
+    if (!d_scaled_labels) { e.stage_result.reserve((size_t)n * plane * 2); d_scaled_labels = e.stage_result.as<uint16_t>(); }
+    if (batch) e.reserve_infer_batch(n, sh, sw, tiles, d_blended != nullptr);
+    e.resize_image_batch(d_images, n, height, width, e.stage_image.as<uint8_t>(), sh, sw);
+    forward(e.stage_image.as<uint8_t>(), d_scaled_labels);
+    e.resize_labels_batch(d_scaled_labels, n, sh, sw, d_results, height, width);
+}
+}  // namespace
 
 int anh_infer_scaled_device(anh_runtime* h, const uint8_t* d_image, int height, int width, double downscaling_factor, const double* gains,
                             const anh_tiling_params* tiling, uint16_t* d_result, uint16_t* d_scaled_labels, float* d_blended) {
     return guarded([&] {
         ANH_REQUIRE(h && d_image && d_result, "null argument");
-        int sh = 0, sw = 0;
-        scaled_dims_checked(height, width, downscaling_factor, sh, sw);
-        DeviceScope scope(h->reps.device_of(0));
-        Engine& e = h->reps.engine(0);
-        const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
-        const size_t plane = (size_t)sh * sw;
-        const std::vector<anh_tile> tiles = tiles_for(tiling, sw, sh);
-        if (!d_blended) { e.stage_blended.reserve(plane * K * 4); d_blended = e.stage_blended.as<float>(); }
-        if (downscaling_factor == 1.0) {   // the host's bilinear returns early at scale 1, nearest neighbour at equal size is the identity
-            e.infer_device(d_image, height, width, gains, tiles, d_result, d_blended, /*whole_image=*/true);
-            if (d_scaled_labels) HIP_CHECK(hipMemcpyAsync(d_scaled_labels, d_result, plane * 2, hipMemcpyDeviceToDevice, e.stream));
-            return;
-        }
-        e.stage_image.reserve(plane * C);
-        if (!d_scaled_labels) { e.stage_result.reserve(plane * 2); d_scaled_labels = e.stage_result.as<uint16_t>(); }
-        e.resize_image(d_image, height, width, e.stage_image.as<uint8_t>(), sh, sw);
-        e.infer_device(e.stage_image.as<uint8_t>(), sh, sw, gains, tiles, d_scaled_labels, d_blended, /*whole_image=*/true);
-        e.resize_labels(d_scaled_labels, sh, sw, d_result, height, width);
+        infer_scaled_on_device(h, false, d_image, 1, height, width, downscaling_factor, gains, tiling, d_result, d_scaled_labels, d_blended);
     });
 }
 
@@ -936,47 +1018,7 @@ int anh_infer_scaled(anh_runtime* h, const uint8_t* image, int height, int width
         ANH_REQUIRE(h && image && result, "null argument");
         int sh = 0, sw = 0;
         scaled_dims_checked(height, width, downscaling_factor, sh, sw);
-        const size_t plane = (size_t)sh * sw, full = (size_t)height * width;
-        if (downscaling_factor == 1.0) {   // exactly anh_infer: the host's bilinear returns early at scale 1, nearest neighbour at equal size is the identity
-            const int rc = anh_infer(h, image, height, width, gains, detection_levels, tiling, result, blended_out);
-            if (rc != ANH_OK) fail(rc, g_error);
-            if (scaled_labels) std::memcpy(scaled_labels, result, full * 2);
-            return;
-        }
-        DeviceScope scope(h->reps.device_of(0));
-        Engine& e = h->reps.engine(0);
-        const int K = e.spec.cfg.classes, C = e.spec.cfg.in_channels;
-        const std::vector<anh_tile> tiles = tiles_for(tiling, sw, sh);
-        const bool use_det = detection_requested(detection_levels, K);
-        e.stage_original.reserve(full * C);
-        e.stage_image.reserve(plane * C);
-        e.stage_blended.reserve(plane * K * 4);
-        e.stage_result.reserve(plane * 2);
-        e.stage_upsampled.reserve(full * 2);
-        if (h->reps.size() > 1 && !use_det && tiles.size() >= 2) {
-            // the sharded path (infer_multi): every replica shrinks the image itself; the merged map is assembled on the host from the
-            // owners of its tiles, as for anh_infer, and replica 0 blows it up
-            std::vector<uint16_t> merged_own;
-            uint16_t* merged = scaled_labels;
-            if (!merged) { merged_own.resize(plane); merged = merged_own.data(); }
-            infer_multi(h, nullptr, sh, sw, gains, tiles, merged, blended_out, image, height, width);
-            HIP_CHECK(hipMemcpyAsync(e.stage_result.p, merged, plane * 2, hipMemcpyHostToDevice, e.stream));
-            e.resize_labels(e.stage_result.as<uint16_t>(), sh, sw, e.stage_upsampled.as<uint16_t>(), height, width);
-            HIP_CHECK(hipMemcpyAsync(result, e.stage_upsampled.p, full * 2, hipMemcpyDeviceToHost, e.stream));
-            e.synchronize();
-            return;
-        }
-        // one stream: original image up, shrink, tiles, (detection-level filter at the net's resolution, as the reference runs it before
-        // resize_label_image), blow the map up, original-size map down
-        HIP_CHECK(hipMemcpyAsync(e.stage_original.p, image, full * C, hipMemcpyHostToDevice, e.stream));
-        e.resize_image(e.stage_original.as<uint8_t>(), height, width, e.stage_image.as<uint8_t>(), sh, sw);
-        e.infer_device(e.stage_image.as<uint8_t>(), sh, sw, gains, tiles, e.stage_result.as<uint16_t>(), e.stage_blended.as<float>(), /*whole_image=*/true);
-        if (use_det) apply_detection_levels(e, detection_levels, K, sh, sw);
-        e.resize_labels(e.stage_result.as<uint16_t>(), sh, sw, e.stage_upsampled.as<uint16_t>(), height, width);
-        HIP_CHECK(hipMemcpyAsync(result, e.stage_upsampled.p, full * 2, hipMemcpyDeviceToHost, e.stream));
-        if (scaled_labels) HIP_CHECK(hipMemcpyAsync(scaled_labels, e.stage_result.p, plane * 2, hipMemcpyDeviceToHost, e.stream));
-        if (blended_out) HIP_CHECK(hipMemcpyAsync(blended_out, e.stage_blended.p, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
-        e.synchronize();
+        run_host_infer(h, HostInfer(h, &image, 1, false, height, width, downscaling_factor, sh, sw, gains, detection_levels, tiling, &result, &scaled_labels, &blended_out));
     });
 }
 
@@ -985,7 +1027,7 @@ int anh_resize_image_batch_device(const uint8_t* d_src, int count, int channels,
     return guarded([&] {
         ANH_REQUIRE(count >= 1, "resize_image: the batch needs at least one image");
         ANH_REQUIRE(d_src && d_dst, "null argument");
-        ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1 && src_h <= 32768 && src_w <= 32768 && dst_h <= 32768 && dst_w <= 32768, "resize_image: sides must be within 1..32768");
+        require_resize_sides("resize_image", src_h, src_w, dst_h, dst_w);
         launch_resize_image_bilinear_batch(d_src, count, channels, src_h, src_w, d_dst, dst_h, dst_w, (hipStream_t)hip_stream);
     });
 }
@@ -994,7 +1036,7 @@ int anh_resize_labels_batch_device(const uint16_t* d_src, int count, int src_h, 
     return guarded([&] {
         ANH_REQUIRE(count >= 1, "resize_labels: the batch needs at least one label image");
         ANH_REQUIRE(d_src && d_dst, "null argument");
-        ANH_REQUIRE(src_h >= 1 && src_w >= 1 && dst_h >= 1 && dst_w >= 1 && src_h <= 32768 && src_w <= 32768 && dst_h <= 32768 && dst_w <= 32768, "resize_labels: sides must be within 1..32768");
+        require_resize_sides("resize_labels", src_h, src_w, dst_h, dst_w);
         launch_resize_labels_nearest_batch(d_src, count, src_h, src_w, d_dst, dst_h, dst_w, (hipStream_t)hip_stream);
     });
 }
@@ -1004,26 +1046,7 @@ int anh_infer_scaled_batch_device(anh_runtime* h, const uint8_t* d_images, int n
     return guarded([&] {
         ANH_REQUIRE(n >= 1, "infer_batch: the batch needs at least one image");
         ANH_REQUIRE(h && d_images && d_results, "null argument");
-        int sh = 0, sw = 0;
-        scaled_dims_checked(height, width, downscaling_factor, sh, sw);
-        DeviceScope scope(h->reps.device_of(0));
-        Engine& e = h->reps.engine(0);
-        const int C = e.spec.cfg.in_channels;
-        const size_t plane = (size_t)sh * sw;
-        const std::vector<anh_tile> tiles = tiles_for(tiling, sw, sh);
-        if (downscaling_factor == 1.0) {   // as anh_infer_scaled_device: no resize at scale 1
-            e.infer_batch_device(d_images, n, height, width, gains, tiles, d_results, d_blended);
-            if (d_scaled_labels) HIP_CHECK(hipMemcpyAsync(d_scaled_labels, d_results, (size_t)n * plane * 2, hipMemcpyDeviceToDevice, e.stream));
-            return;
-        }
-        // reserved before the first kernel; infer_batch_device reserves its own (planes, logits) before its first kernel and writes nothing
-        // the shrink does not own, so a batch that cannot fit has only shrunk images into a stage buffer
-        e.stage_image.reserve((size_t)n * plane * C);
-        if (!d_scaled_labels) { e.stage_result.reserve((size_t)n * plane * 2); d_scaled_labels = e.stage_result.as<uint16_t>(); }
-        e.reserve_infer_batch(n, sh, sw, tiles, d_blended != nullptr);
-        e.resize_image_batch(d_images, n, height, width, e.stage_image.as<uint8_t>(), sh, sw);
-        e.infer_batch_device(e.stage_image.as<uint8_t>(), n, sh, sw, gains, tiles, d_scaled_labels, d_blended);
-        e.resize_labels_batch(d_scaled_labels, n, sh, sw, d_results, height, width);
+        infer_scaled_on_device(h, true, d_images, n, height, width, downscaling_factor, gains, tiling, d_results, d_scaled_labels, d_blended);
     });
 }
 
@@ -1038,58 +1061,7 @@ int anh_infer_scaled_batch(anh_runtime* h, const uint8_t* const* images, int n, 
         int sh = 0, sw = 0;
         scaled_dims_checked(height, width, downscaling_factor, sh, sw);
         for (int i = 0; i < n; ++i) ANH_REQUIRE(images[i] && results[i], "infer_batch: null image or result");
-        const size_t plane = (size_t)sh * sw, full = (size_t)height * width;
-        if (downscaling_factor == 1.0) {   // exactly anh_infer_batch, as anh_infer_scaled is exactly anh_infer
-            const int rc = anh_infer_batch(h, images, n, height, width, gains, detection_levels, tiling, results, blended_out);
-            if (rc != ANH_OK) fail(rc, g_error);
-            if (scaled_labels) for (int i = 0; i < n; ++i) if (scaled_labels[i]) std::memcpy(scaled_labels[i], results[i], full * 2);
-            return;
-        }
-        const size_t R = h->reps.size();
-        if ((size_t)n < R) {   // fewer images than replicas: image by image, as anh_infer_scaled serves them
-            for (int i = 0; i < n; ++i) {
-                const int rc = anh_infer_scaled(h, images[i], height, width, downscaling_factor, gains, detection_levels, tiling, results[i],
-                                                scaled_labels ? scaled_labels[i] : nullptr, blended_out ? blended_out[i] : nullptr);
-                if (rc != ANH_OK) fail(rc, g_error);
-            }
-            return;
-        }
-        const int K = h->reps.engine(0).spec.cfg.classes, C = h->reps.engine(0).spec.cfg.in_channels;
-        const std::vector<anh_tile> tiles = tiles_for(tiling, sw, sh);
-        const bool use_det = detection_requested(detection_levels, K);
-        // every replica takes a contiguous share of the images and shrinks, infers and blows up its own: nothing is exchanged
-        h->reps.each([&](size_t r, Engine& e) {
-            int64_t lo = 0, hi = 0;
-            shard_range((int64_t)n, (int)R, (int)r, lo, hi);
-            const int m = (int)(hi - lo);
-            if (m <= 0) return;
-            bool planes = use_det;   // the filter reads the planes
-            if (blended_out) for (int64_t i = lo; i < hi; ++i) planes = planes || blended_out[i] != nullptr;
-            e.stage_original.reserve((size_t)m * full * C);
-            e.stage_image.reserve((size_t)m * plane * C);
-            e.stage_result.reserve((size_t)m * plane * 2);
-            e.stage_upsampled.reserve((size_t)m * full * 2);
-            if (planes) e.stage_blended.reserve((size_t)m * plane * K * 4);
-            if (use_det) e.stage_out.reserve(detection_scratch_bytes(plane, K));
-            e.reserve_infer_batch(m, sh, sw, tiles, planes);
-            for (int i = 0; i < m; ++i)
-                HIP_CHECK(hipMemcpyAsync(e.stage_original.as<uint8_t>() + (size_t)i * full * C, images[lo + i], full * C, hipMemcpyHostToDevice, e.stream));
-            float* d_planes = planes ? e.stage_blended.as<float>() : nullptr;
-            uint16_t* d_labels = e.stage_result.as<uint16_t>();
-            uint16_t* d_up = e.stage_upsampled.as<uint16_t>();
-            e.resize_image_batch(e.stage_original.as<uint8_t>(), m, height, width, e.stage_image.as<uint8_t>(), sh, sw);
-            e.infer_batch_device(e.stage_image.as<uint8_t>(), m, sh, sw, gains, tiles, d_labels, d_planes);
-            if (use_det) for (int i = 0; i < m; ++i) apply_detection_levels(e, detection_levels, K, sh, sw, d_planes + (size_t)i * K * plane, d_labels + (size_t)i * plane);
-            e.resize_labels_batch(d_labels, m, sh, sw, d_up, height, width);
-            for (int i = 0; i < m; ++i) {
-                HIP_CHECK(hipMemcpyAsync(results[lo + i], d_up + (size_t)i * full, full * 2, hipMemcpyDeviceToHost, e.stream));
-                if (scaled_labels && scaled_labels[lo + i])
-                    HIP_CHECK(hipMemcpyAsync(scaled_labels[lo + i], d_labels + (size_t)i * plane, plane * 2, hipMemcpyDeviceToHost, e.stream));
-                if (blended_out && blended_out[lo + i])
-                    HIP_CHECK(hipMemcpyAsync(blended_out[lo + i], d_planes + (size_t)i * K * plane, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
-            }
-            e.synchronize();
-        });
+        run_host_infer(h, HostInfer(h, images, n, true, height, width, downscaling_factor, sh, sw, gains, detection_levels, tiling, results, scaled_labels, blended_out));
     });
 }
 

@@ -341,89 +341,105 @@ class RuntimeNet(_Profiled):
         return out
 
 
-def annonet_infer(net, input_image, gains=None, detection_levels=None, tiling_parameters=None, want_blended=False):
-    """annonet_infer() (annonet_infer.h:34-42): returns the u16 label image (and the blended class planes)."""
-    img = np.ascontiguousarray(input_image, dtype=np.uint8)
-    if img.ndim == 2:
-        img = img[:, :, None]
-    H, W, c = img.shape
+# ---- what the inference wrappers share: their arguments as the C ABI takes them ----
+def _f64(values):
+    return np.ascontiguousarray(values, dtype=np.float64) if values is not None else None
+
+
+def _images(net, input_images):
+    """u8 images of ONE size -> (contiguous [H,W,C] arrays, H, W); a [H,W] image gets its channel axis"""
+    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in input_images]
+    imgs = [im[:, :, None] if im.ndim == 2 else im for im in imgs]
+    if imgs and any(im.shape != imgs[0].shape for im in imgs):
+        raise AnnonetHipError(1, "the images of a batch must have one size and channel count")
+    H, W, c = imgs[0].shape if imgs else (0, 0, net.cfg.in_channels)
     if c != net.cfg.in_channels:
         raise AnnonetHipError(1, "channel count does not match the net input")
-    K = net.cfg.classes
-    res = np.empty((H, W), np.uint16)
-    bl = np.empty((K, H, W), np.float32) if want_blended else None
-    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
-    d = np.ascontiguousarray(detection_levels, dtype=np.float64) if detection_levels is not None else None
-    if g is not None and g.size != K or d is not None and d.size != K:
+    return imgs, H, W
+
+
+def _per_class(net, gains, detection_levels):
+    """gains and detection levels as f64 arrays (or None), one value per class of the net"""
+    g, d = _f64(gains), _f64(detection_levels)
+    if g is not None and g.size != net.cfg.classes or d is not None and d.size != net.cfg.classes:
         raise AnnonetHipError(1, "gains / detection levels need one value per class")
-    tp = tiling_parameters._c() if tiling_parameters is not None else None
-    check(net.L.anh_infer(net.h, _ptr(img), H, W, _ptr(g), _ptr(d), C.byref(tp) if tp is not None else None, _ptr(res), _ptr(bl)))
+    return g, d
+
+
+def _tiling_ref(tiling_parameters):
+    """anh_tiling_params by reference (None: the image is one tile)"""
+    return C.byref(tiling_parameters._c()) if tiling_parameters is not None else None
+
+
+def _tile_array(tiles):
+    """list of (full, unique) rectangles -> anh_tile[]"""
+    arr = (_lib.Tile * max(len(tiles), 1))()
+    for i, (full, uniq) in enumerate(tiles):
+        arr[i].full_rect = _lib.Rect(*full)
+        arr[i].unique_rect = _lib.Rect(*uniq)
+    return arr
+
+
+def _per_image(want, n):
+    """a want_* argument, one boolean for all images or a list with one per image -> list of n"""
+    return list(want) if isinstance(want, (list, tuple)) else [bool(want)] * n
+
+
+def _outputs(want, shape, dtype):
+    return [np.empty(shape, dtype) if w else None for w in want]
+
+
+def _ptrs(arrays, n):
+    """the arrays' addresses as a void*[n] (NULL where an entry is None)"""
+    return (C.c_void_p * max(n, 1))(*[a.ctypes.data if a is not None else None for a in arrays])
+
+
+def annonet_infer(net, input_image, gains=None, detection_levels=None, tiling_parameters=None, want_blended=False):
+    """annonet_infer() (annonet_infer.h:34-42): returns the u16 label image (and the blended class planes)."""
+    (img,), H, W = _images(net, [input_image])
+    g, d = _per_class(net, gains, detection_levels)
+    res = np.empty((H, W), np.uint16)
+    bl = np.empty((net.cfg.classes, H, W), np.float32) if want_blended else None
+    check(net.L.anh_infer(net.h, _ptr(img), H, W, _ptr(g), _ptr(d), _tiling_ref(tiling_parameters), _ptr(res), _ptr(bl)))
     return (res, bl) if want_blended else res
 
 
 def annonet_infer_device(net, d_image_ptr, height, width, d_labels_ptr, d_blended_ptr, gains=None, tiling_parameters=None, tiles=None):
     """annonet_infer() with the image, the label map and the blended planes resident in HBM (device pointers as ints).
     `tiles` (list of (full, unique) rects) restricts the call to a shard of the tile list (multi-GPU inference)."""
-    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
-    tp = tiling_parameters._c() if tiling_parameters is not None else None
-    arr, n = None, 0
-    if tiles is not None:
-        n = len(tiles)
-        arr = (_lib.Tile * max(n, 1))()
-        for i, (full, uniq) in enumerate(tiles):
-            arr[i].full_rect = _lib.Rect(*full)
-            arr[i].unique_rect = _lib.Rect(*uniq)
-    check(net.L.anh_infer_device(net.h, d_image_ptr, height, width, _ptr(g), C.byref(tp) if tp is not None else None, arr, n, d_labels_ptr, d_blended_ptr))
+    arr, n = (_tile_array(tiles), len(tiles)) if tiles is not None else (None, 0)
+    check(net.L.anh_infer_device(net.h, d_image_ptr, height, width, _ptr(_f64(gains)), _tiling_ref(tiling_parameters), arr, n, d_labels_ptr, d_blended_ptr))
 
 
 def annonet_infer_batch(net, input_images, gains=None, detection_levels=None, tiling_parameters=None, want_blended=False):
     """annonet_infer() over several images of ONE size in one call (anh_infer_batch): a list of u8 images (or an array [n,H,W,C]) ->
     list of u16 label images (and, with want_blended, the list of their blended class planes).  want_blended may also be a list of
     booleans, one per image.  Every image's result equals annonet_infer() of that image alone, bit for bit."""
-    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in input_images]
-    imgs = [im[:, :, None] if im.ndim == 2 else im for im in imgs]
+    g, d = _per_class(net, gains, detection_levels)
+    imgs, H, W = _images(net, input_images)
     n = len(imgs)
-    K = net.cfg.classes
-    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
-    d = np.ascontiguousarray(detection_levels, dtype=np.float64) if detection_levels is not None else None
-    if g is not None and g.size != K or d is not None and d.size != K:
-        raise AnnonetHipError(1, "gains / detection levels need one value per class")
-    if n and any(im.shape != imgs[0].shape for im in imgs):
-        raise AnnonetHipError(1, "the images of a batch must have one size and channel count")
-    if n and imgs[0].shape[2] != net.cfg.in_channels:
-        raise AnnonetHipError(1, "channel count does not match the net input")
-    H, W = imgs[0].shape[:2] if n else (0, 0)
-    want = list(want_blended) if isinstance(want_blended, (list, tuple)) else [bool(want_blended)] * n
-    res = [np.empty((H, W), np.uint16) for _ in range(n)]
-    bl = [np.empty((K, H, W), np.float32) if w else None for w in want]
-    ptrs = lambda arrays: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a is not None else None for a in arrays])
-    tp = tiling_parameters._c() if tiling_parameters is not None else None
-    check(net.L.anh_infer_batch(net.h, ptrs(imgs), n, H, W, _ptr(g), _ptr(d), C.byref(tp) if tp is not None else None, ptrs(res),
-                                ptrs(bl) if any(want) else None))
+    want = _per_image(want_blended, n)
+    res = _outputs([True] * n, (H, W), np.uint16)
+    bl = _outputs(want, (net.cfg.classes, H, W), np.float32)
+    check(net.L.anh_infer_batch(net.h, _ptrs(imgs, n), n, H, W, _ptr(g), _ptr(d), _tiling_ref(tiling_parameters), _ptrs(res, n), _ptrs(bl, n) if any(want) else None))
     return (res, bl) if any(want) or want_blended else res
 
 
 def annonet_infer_batch_device(net, d_images_ptr, n, height, width, d_labels_ptr, d_blended_ptr=0, gains=None, tiling_parameters=None):
     """annonet_infer_batch with the images [n,H,W,C], the label maps [n,H,W] and (optionally) the planes [n,K,H,W] resident in HBM
     (device pointers as ints); enqueued on the handle's stream, not synchronised."""
-    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
-    tp = tiling_parameters._c() if tiling_parameters is not None else None
-    check(net.L.anh_infer_batch_device(net.h, d_images_ptr, n, height, width, _ptr(g), C.byref(tp) if tp is not None else None, d_labels_ptr, d_blended_ptr or None))
+    check(net.L.anh_infer_batch_device(net.h, d_images_ptr, n, height, width, _ptr(_f64(gains)), _tiling_ref(tiling_parameters), d_labels_ptr, d_blended_ptr or None))
 
 
 def labels_from_logits_device(net, d_logits_ptr, count, classes, win_height, win_width, top, left, height, width, d_labels_ptr, gains=None):
     """find_label straight from the logits [count,classes,win_height,win_width] of whole-image tiles whose window starts at (left, top):
     label maps [count,height,width] (anh_labels_from_logits_device)."""
-    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
-    check(net.L.anh_labels_from_logits_device(net.h, d_logits_ptr, count, classes, win_height, win_width, top, left, height, width, _ptr(g), d_labels_ptr))
+    check(net.L.anh_labels_from_logits_device(net.h, d_logits_ptr, count, classes, win_height, win_width, top, left, height, width, _ptr(_f64(gains)), d_labels_ptr))
 
 
 def infer_batch_plan(tiles, n_images, levels, cap):
     """anh_infer_batch_plan: tiles = one image's list of (full, unique) rectangles -> the forward batches, each a list of (image, tile)."""
-    arr = (_lib.Tile * max(len(tiles), 1))()
-    for i, (full, uniq) in enumerate(tiles):
-        arr[i].full_rect = _lib.Rect(*full)
-        arr[i].unique_rect = _lib.Rect(*uniq)
+    arr = _tile_array(tiles)
     pairs, sizes, nb = C.POINTER(C.c_int)(), C.POINTER(C.c_int)(), C.c_size_t()
     L = _lib.lib()
     check(L.anh_infer_batch_plan(arr, len(tiles), n_images, levels, cap, C.byref(pairs), C.byref(sizes), C.byref(nb)))
@@ -449,23 +465,13 @@ def annonet_infer_scaled(net, input_image, downscaling_factor, gains=None, detec
     """read_sample's resize (annonet.cpp:153) + annonet_infer() + resize_label_image (annonet_infer_main.cpp:413) on the device: the image
     comes at its original size, the label map comes back at that size.  Returns the map, then (when asked for) the map at the net's
     resolution and the blended class planes at the net's resolution."""
-    img = np.ascontiguousarray(input_image, dtype=np.uint8)
-    if img.ndim == 2:
-        img = img[:, :, None]
-    H, W, c = img.shape
-    if c != net.cfg.in_channels:
-        raise AnnonetHipError(1, "channel count does not match the net input")
-    K = net.cfg.classes
-    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
-    d = np.ascontiguousarray(detection_levels, dtype=np.float64) if detection_levels is not None else None
-    if g is not None and g.size != K or d is not None and d.size != K:
-        raise AnnonetHipError(1, "gains / detection levels need one value per class")
+    (img,), H, W = _images(net, [input_image])
+    g, d = _per_class(net, gains, detection_levels)
     sh, sw = scaled_dims(H, W, downscaling_factor)
     res = np.empty((H, W), np.uint16)
     scaled = np.empty((sh, sw), np.uint16) if want_scaled else None
-    bl = np.empty((K, sh, sw), np.float32) if want_blended else None
-    tp = tiling_parameters._c() if tiling_parameters is not None else None
-    check(net.L.anh_infer_scaled(net.h, _ptr(img), H, W, downscaling_factor, _ptr(g), _ptr(d), C.byref(tp) if tp is not None else None, _ptr(res), _ptr(scaled), _ptr(bl)))
+    bl = np.empty((net.cfg.classes, sh, sw), np.float32) if want_blended else None
+    check(net.L.anh_infer_scaled(net.h, _ptr(img), H, W, downscaling_factor, _ptr(g), _ptr(d), _tiling_ref(tiling_parameters), _ptr(res), _ptr(scaled), _ptr(bl)))
     out = (res,) + ((scaled,) if want_scaled else ()) + ((bl,) if want_blended else ())
     return out if len(out) > 1 else res
 
@@ -473,9 +479,7 @@ def annonet_infer_scaled(net, input_image, downscaling_factor, gains=None, detec
 def annonet_infer_scaled_device(net, d_image_ptr, height, width, downscaling_factor, d_labels_ptr, d_scaled_labels_ptr=0, d_blended_ptr=0, gains=None, tiling_parameters=None):
     """annonet_infer_scaled with the original-size image, the original-size label map and (optionally) the map and the planes at the
     net's resolution resident in HBM (device pointers as ints); enqueued on the handle's stream, not synchronised."""
-    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
-    tp = tiling_parameters._c() if tiling_parameters is not None else None
-    check(net.L.anh_infer_scaled_device(net.h, d_image_ptr, height, width, downscaling_factor, _ptr(g), C.byref(tp) if tp is not None else None,
+    check(net.L.anh_infer_scaled_device(net.h, d_image_ptr, height, width, downscaling_factor, _ptr(_f64(gains)), _tiling_ref(tiling_parameters),
                                         d_labels_ptr, d_scaled_labels_ptr or None, d_blended_ptr or None))
 
 
@@ -485,29 +489,16 @@ def annonet_infer_scaled_batch(net, input_images, downscaling_factor, gains=None
     then (when asked for) the list of maps at the net's resolution and the list of blended class planes at the net's resolution.
     want_scaled / want_blended may also be lists of booleans, one per image (None where not asked for).  Every image's results equal
     annonet_infer_scaled() of that image alone, bit for bit."""
-    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in input_images]
-    imgs = [im[:, :, None] if im.ndim == 2 else im for im in imgs]
+    g, d = _per_class(net, gains, detection_levels)
+    imgs, H, W = _images(net, input_images)
     n = len(imgs)
-    K = net.cfg.classes
-    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
-    d = np.ascontiguousarray(detection_levels, dtype=np.float64) if detection_levels is not None else None
-    if g is not None and g.size != K or d is not None and d.size != K:
-        raise AnnonetHipError(1, "gains / detection levels need one value per class")
-    if n and any(im.shape != imgs[0].shape for im in imgs):
-        raise AnnonetHipError(1, "the images of a batch must have one size and channel count")
-    if n and imgs[0].shape[2] != net.cfg.in_channels:
-        raise AnnonetHipError(1, "channel count does not match the net input")
-    H, W = imgs[0].shape[:2] if n else (0, 0)
     sh, sw = scaled_dims(H, W, downscaling_factor) if n else (0, 0)
-    per_image = lambda want: list(want) if isinstance(want, (list, tuple)) else [bool(want)] * n
-    ws, wb = per_image(want_scaled), per_image(want_blended)
-    res = [np.empty((H, W), np.uint16) for _ in range(n)]
-    sc = [np.empty((sh, sw), np.uint16) if w else None for w in ws]
-    bl = [np.empty((K, sh, sw), np.float32) if w else None for w in wb]
-    ptrs = lambda arrays: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a is not None else None for a in arrays])
-    tp = tiling_parameters._c() if tiling_parameters is not None else None
-    check(net.L.anh_infer_scaled_batch(net.h, ptrs(imgs), n, H, W, downscaling_factor, _ptr(g), _ptr(d), C.byref(tp) if tp is not None else None,
-                                       ptrs(res), ptrs(sc) if any(ws) else None, ptrs(bl) if any(wb) else None))
+    ws, wb = _per_image(want_scaled, n), _per_image(want_blended, n)
+    res = _outputs([True] * n, (H, W), np.uint16)
+    sc = _outputs(ws, (sh, sw), np.uint16)
+    bl = _outputs(wb, (net.cfg.classes, sh, sw), np.float32)
+    check(net.L.anh_infer_scaled_batch(net.h, _ptrs(imgs, n), n, H, W, downscaling_factor, _ptr(g), _ptr(d), _tiling_ref(tiling_parameters),
+                                       _ptrs(res, n), _ptrs(sc, n) if any(ws) else None, _ptrs(bl, n) if any(wb) else None))
     out = (res,) + ((sc,) if any(ws) or want_scaled else ()) + ((bl,) if any(wb) or want_blended else ())
     return out if len(out) > 1 else res
 
@@ -517,9 +508,7 @@ def annonet_infer_scaled_batch_device(net, d_images_ptr, n, height, width, downs
     """annonet_infer_scaled_batch with the original-size images [n,H,W,C], the original-size label maps [n,H,W] and (optionally) the maps
     [n,sh,sw] and the planes [n,K,sh,sw] at the net's resolution resident in HBM (device pointers as ints); enqueued on the handle's
     stream, not synchronised."""
-    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
-    tp = tiling_parameters._c() if tiling_parameters is not None else None
-    check(net.L.anh_infer_scaled_batch_device(net.h, d_images_ptr, n, height, width, downscaling_factor, _ptr(g), C.byref(tp) if tp is not None else None,
+    check(net.L.anh_infer_scaled_batch_device(net.h, d_images_ptr, n, height, width, downscaling_factor, _ptr(_f64(gains)), _tiling_ref(tiling_parameters),
                                               d_labels_ptr, d_scaled_labels_ptr or None, d_blended_ptr or None))
 
 
@@ -628,7 +617,7 @@ def label_blobs(label_map, prefill=None, net=None):
 
 def regions_device(net, d_labels_ptr, d_blended_ptr, classes, height, width, detection_levels=None, apply_filter=False, d_blobs_ptr=0):
     """anh_regions_device on resident buffers (device pointers as ints): the region table as a numpy structured array (REGION_DTYPE)."""
-    d = np.ascontiguousarray(detection_levels, dtype=np.float64) if detection_levels is not None else None
+    d = _f64(detection_levels)
     if d is not None and d.size != classes:
         raise AnnonetHipError(1, "detection levels need one value per class")
     table, n = C.POINTER(_lib.Region)(), C.c_size_t()
@@ -659,23 +648,13 @@ def regions(label_map, blended, detection_levels=None, apply_filter=False, prefi
 def annonet_infer_regions(net, input_image, gains=None, detection_levels=None, tiling_parameters=None, want_blobs=False, want_blended=False):
     """annonet_infer() plus the region table of its unfiltered label map (anh_infer_regions): returns (label map, table as a numpy
     structured array of REGION_DTYPE), followed by the u32 blob map and the blended planes when asked for."""
-    img = np.ascontiguousarray(input_image, dtype=np.uint8)
-    if img.ndim == 2:
-        img = img[:, :, None]
-    H, W, c = img.shape
-    if c != net.cfg.in_channels:
-        raise AnnonetHipError(1, "channel count does not match the net input")
-    K = net.cfg.classes
+    (img,), H, W = _images(net, [input_image])
+    g, d = _per_class(net, gains, detection_levels)
     res = np.empty((H, W), np.uint16)
     blobs = np.empty((H, W), np.uint32) if want_blobs else None
-    bl = np.empty((K, H, W), np.float32) if want_blended else None
-    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
-    d = np.ascontiguousarray(detection_levels, dtype=np.float64) if detection_levels is not None else None
-    if g is not None and g.size != K or d is not None and d.size != K:
-        raise AnnonetHipError(1, "gains / detection levels need one value per class")
-    tp = tiling_parameters._c() if tiling_parameters is not None else None
+    bl = np.empty((net.cfg.classes, H, W), np.float32) if want_blended else None
     table, n = C.POINTER(_lib.Region)(), C.c_size_t()
-    check(net.L.anh_infer_regions(net.h, _ptr(img), H, W, _ptr(g), _ptr(d), C.byref(tp) if tp is not None else None, _ptr(res), _ptr(blobs), _ptr(bl),
+    check(net.L.anh_infer_regions(net.h, _ptr(img), H, W, _ptr(g), _ptr(d), _tiling_ref(tiling_parameters), _ptr(res), _ptr(blobs), _ptr(bl),
                                   C.byref(table), C.byref(n)))
     out = [res, _take_regions(net.L, table, n.value)]
     if want_blobs:
@@ -687,8 +666,7 @@ def annonet_infer_regions(net, input_image, gains=None, detection_levels=None, t
 
 def argmax_device(net, d_blended_ptr, height, width, row0, row1, d_labels_ptr, gains=None):
     """find_label (annonet_infer.cpp:170-185) over rows [row0, row1) of device-resident blended planes."""
-    g = np.ascontiguousarray(gains, dtype=np.float64) if gains is not None else None
-    check(net.L.anh_argmax_device(net.h, d_blended_ptr, height, width, row0, row1, _ptr(g), d_labels_ptr))
+    check(net.L.anh_argmax_device(net.h, d_blended_ptr, height, width, row0, row1, _ptr(_f64(gains)), d_labels_ptr))
 
 
 class TrainingNet(_Profiled):

@@ -6,6 +6,7 @@
 #define ANNONET_INFER_HIP_H
 
 #include <cstdlib>
+#include <string>
 
 #include "NetPimpl.h"
 #include "tiling/dlib-wrapper.h"
@@ -37,29 +38,61 @@ struct annonet_infer_temp {  // annonet_infer.h:26-32; the GPU path keeps its sc
     bool keep_connected_blobs = false;
 };
 
+namespace annonet_infer_hip_detail {
+// the net's class count, once the sizes of the per-class arguments (and of a batch) are checked; `fn` names the calling function in the message
+inline int classes_checked(NetPimpl::RuntimeNet& net, const char* fn, const std::vector<double>& gains, const std::vector<double>& detection_levels,
+                           const std::vector<NetPimpl::input_type>* batch = nullptr) {
+    anh_net_config cfg;
+    NetPimpl::check(anh_runtime_config(net.handle(), &cfg));
+    if (batch && batch->empty()) throw std::runtime_error(std::string(fn) + ": the batch needs at least one image");
+    if (!gains.empty() && (int)gains.size() != cfg.classes) throw std::runtime_error(std::string(fn) + ": one gain per class expected");
+    if (!detection_levels.empty() && (int)detection_levels.size() != cfg.classes) throw std::runtime_error(std::string(fn) + ": one detection level per class expected");
+    return cfg.classes;
+}
+inline const double* data_or_null(const std::vector<double>& v) { return v.empty() ? nullptr : v.data(); }
+inline anh_tiling_params to_params(const tiling::parameters& p) { return anh_tiling_params{p.max_tile_width, p.max_tile_height, p.overlap_x, p.overlap_y}; }
+inline const uint8_t* pixels(const NetPimpl::input_type& image) { return reinterpret_cast<const uint8_t*>(&*image.begin()); }
+// planes [K][h][w] as they came back -> temp.blended_output
+inline void store_planes(annonet_infer_temp& temp, const std::vector<float>& planes, int K, int h, int w) {
+    temp.blended_output.resize(K);
+    for (int k = 0; k < K; ++k) {
+        temp.blended_output[k].set_size(h, w);
+        std::copy(planes.begin() + (size_t)k * h * w, planes.begin() + (size_t)(k + 1) * h * w, temp.blended_output[k].begin());
+    }
+}
+// the image and result pointers of a (non-empty) batch of ONE size; the results are sized here
+struct batch_pointers {
+    int n, H, W;
+    std::vector<const uint8_t*> images;
+    std::vector<uint16_t*> results;
+    std::vector<float*> planes_of;   // all null but the last image's, when the planes are kept
+    batch_pointers(const char* fn, const std::vector<NetPimpl::input_type>& input_images, std::vector<dlib::matrix<uint16_t>>& result_images) {
+        n = (int)input_images.size(); H = (int)input_images[0].nr(); W = (int)input_images[0].nc();
+        images.resize((size_t)n); results.resize((size_t)n); planes_of.assign((size_t)n, nullptr);
+        result_images.resize((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            if ((int)input_images[i].nr() != H || (int)input_images[i].nc() != W) throw std::runtime_error(std::string(fn) + ": the images of a batch must have one size");
+            images[i] = pixels(input_images[i]);
+            result_images[i].set_size(H, W);
+            results[i] = &*result_images[i].begin();
+        }
+    }
+};
+}  // namespace annonet_infer_hip_detail
+
 inline void annonet_infer(NetPimpl::RuntimeNet& net, const NetPimpl::input_type& input_image, dlib::matrix<uint16_t>& result_image,
                           annonet_infer_temp& temp, const std::vector<double>& gains = std::vector<double>(),
                           const std::vector<double>& detection_levels = std::vector<double>(),
                           const tiling::parameters& tiling_parameters = tiling::parameters()) {
-    anh_net_config cfg;
-    NetPimpl::check(anh_runtime_config(net.handle(), &cfg));
-    const int K = cfg.classes, H = (int)input_image.nr(), W = (int)input_image.nc();
-    if (!gains.empty() && (int)gains.size() != K) throw std::runtime_error("annonet_infer: one gain per class expected");
-    if (!detection_levels.empty() && (int)detection_levels.size() != K) throw std::runtime_error("annonet_infer: one detection level per class expected");
+    namespace d = annonet_infer_hip_detail;
+    const int K = d::classes_checked(net, "annonet_infer", gains, detection_levels), H = (int)input_image.nr(), W = (int)input_image.nc();
     result_image.set_size(H, W);
     std::vector<float> planes;
     if (temp.keep_blended_output) planes.resize((size_t)K * H * W);
-    anh_tiling_params tp{tiling_parameters.max_tile_width, tiling_parameters.max_tile_height, tiling_parameters.overlap_x, tiling_parameters.overlap_y};
-    NetPimpl::check(anh_infer(net.handle(), reinterpret_cast<const uint8_t*>(&*input_image.begin()), H, W, gains.empty() ? nullptr : gains.data(),
-                              detection_levels.empty() ? nullptr : detection_levels.data(), &tp, &*result_image.begin(),
+    const anh_tiling_params tp = d::to_params(tiling_parameters);
+    NetPimpl::check(anh_infer(net.handle(), d::pixels(input_image), H, W, d::data_or_null(gains), d::data_or_null(detection_levels), &tp, &*result_image.begin(),
                               temp.keep_blended_output ? planes.data() : nullptr));
-    if (temp.keep_blended_output) {
-        temp.blended_output.resize(K);
-        for (int k = 0; k < K; ++k) {
-            temp.blended_output[k].set_size(H, W);
-            std::copy(planes.begin() + (size_t)k * H * W, planes.begin() + (size_t)(k + 1) * H * W, temp.blended_output[k].begin());
-        }
-    }
+    if (temp.keep_blended_output) d::store_planes(temp, planes, K, H, W);
 }
 
 // annonet_infer() that also leaves what the reference computes on the way to its detection-level filter (annonet_infer.cpp:194-223): the
@@ -70,32 +103,22 @@ inline void annonet_infer_regions(NetPimpl::RuntimeNet& net, const NetPimpl::inp
                                   annonet_infer_temp& temp, const std::vector<double>& gains = std::vector<double>(),
                                   const std::vector<double>& detection_levels = std::vector<double>(),
                                   const tiling::parameters& tiling_parameters = tiling::parameters()) {
-    anh_net_config cfg;
-    NetPimpl::check(anh_runtime_config(net.handle(), &cfg));
-    const int K = cfg.classes, H = (int)input_image.nr(), W = (int)input_image.nc();
-    if (!gains.empty() && (int)gains.size() != K) throw std::runtime_error("annonet_infer_regions: one gain per class expected");
-    if (!detection_levels.empty() && (int)detection_levels.size() != K) throw std::runtime_error("annonet_infer_regions: one detection level per class expected");
+    namespace d = annonet_infer_hip_detail;
+    const int K = d::classes_checked(net, "annonet_infer_regions", gains, detection_levels), H = (int)input_image.nr(), W = (int)input_image.nc();
     result_image.set_size(H, W);
     std::vector<float> planes;
     if (temp.keep_blended_output) planes.resize((size_t)K * H * W);
     if (temp.keep_connected_blobs) temp.connected_blobs.set_size(H, W);
     static_assert(sizeof(unsigned int) == sizeof(uint32_t), "connected_blobs receives the u32 blob map as it is");
-    anh_tiling_params tp{tiling_parameters.max_tile_width, tiling_parameters.max_tile_height, tiling_parameters.overlap_x, tiling_parameters.overlap_y};
+    const anh_tiling_params tp = d::to_params(tiling_parameters);
     anh_region* table = nullptr;
     size_t rows = 0;
-    NetPimpl::check(anh_infer_regions(net.handle(), reinterpret_cast<const uint8_t*>(&*input_image.begin()), H, W, gains.empty() ? nullptr : gains.data(),
-                                      detection_levels.empty() ? nullptr : detection_levels.data(), &tp, &*result_image.begin(),
+    NetPimpl::check(anh_infer_regions(net.handle(), d::pixels(input_image), H, W, d::data_or_null(gains), d::data_or_null(detection_levels), &tp, &*result_image.begin(),
                                       temp.keep_connected_blobs ? reinterpret_cast<uint32_t*>(&*temp.connected_blobs.begin()) : nullptr,
                                       temp.keep_blended_output ? planes.data() : nullptr, &table, &rows));
     try { temp.regions.assign(table, table + rows); } catch (...) { anh_free(table); throw; }
     anh_free(table);
-    if (temp.keep_blended_output) {
-        temp.blended_output.resize(K);
-        for (int k = 0; k < K; ++k) {
-            temp.blended_output[k].set_size(H, W);
-            std::copy(planes.begin() + (size_t)k * H * W, planes.begin() + (size_t)(k + 1) * H * W, temp.blended_output[k].begin());
-        }
-    }
+    if (temp.keep_blended_output) d::store_planes(temp, planes, K, H, W);
 }
 
 // annonet_infer() over several images of ONE size in one call (anh_infer_batch): a folder of camera frames that are one tile each runs the
@@ -106,35 +129,15 @@ inline void annonet_infer_batch(NetPimpl::RuntimeNet& net, const std::vector<Net
                                 annonet_infer_temp& temp, const std::vector<double>& gains = std::vector<double>(),
                                 const std::vector<double>& detection_levels = std::vector<double>(),
                                 const tiling::parameters& tiling_parameters = tiling::parameters()) {
-    anh_net_config cfg;
-    NetPimpl::check(anh_runtime_config(net.handle(), &cfg));
-    if (input_images.empty()) throw std::runtime_error("annonet_infer_batch: the batch needs at least one image");
-    const int K = cfg.classes, n = (int)input_images.size(), H = (int)input_images[0].nr(), W = (int)input_images[0].nc();
-    if (!gains.empty() && (int)gains.size() != K) throw std::runtime_error("annonet_infer_batch: one gain per class expected");
-    if (!detection_levels.empty() && (int)detection_levels.size() != K) throw std::runtime_error("annonet_infer_batch: one detection level per class expected");
-    std::vector<const uint8_t*> images((size_t)n);
-    std::vector<uint16_t*> results((size_t)n);
-    std::vector<float*> planes_of((size_t)n, nullptr);
-    result_images.resize((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        if ((int)input_images[i].nr() != H || (int)input_images[i].nc() != W) throw std::runtime_error("annonet_infer_batch: the images of a batch must have one size");
-        images[i] = reinterpret_cast<const uint8_t*>(&*input_images[i].begin());
-        result_images[i].set_size(H, W);
-        results[i] = &*result_images[i].begin();
-    }
+    namespace d = annonet_infer_hip_detail;
+    const int K = d::classes_checked(net, "annonet_infer_batch", gains, detection_levels, &input_images);
+    d::batch_pointers b("annonet_infer_batch", input_images, result_images);
     std::vector<float> planes;
-    if (temp.keep_blended_output) { planes.resize((size_t)K * H * W); planes_of[n - 1] = planes.data(); }
-    anh_tiling_params tp{tiling_parameters.max_tile_width, tiling_parameters.max_tile_height, tiling_parameters.overlap_x, tiling_parameters.overlap_y};
-    NetPimpl::check(anh_infer_batch(net.handle(), images.data(), n, H, W, gains.empty() ? nullptr : gains.data(),
-                                    detection_levels.empty() ? nullptr : detection_levels.data(), &tp, results.data(),
-                                    temp.keep_blended_output ? planes_of.data() : nullptr));
-    if (temp.keep_blended_output) {
-        temp.blended_output.resize(K);
-        for (int k = 0; k < K; ++k) {
-            temp.blended_output[k].set_size(H, W);
-            std::copy(planes.begin() + (size_t)k * H * W, planes.begin() + (size_t)(k + 1) * H * W, temp.blended_output[k].begin());
-        }
-    }
+    if (temp.keep_blended_output) { planes.resize((size_t)K * b.H * b.W); b.planes_of[b.n - 1] = planes.data(); }
+    const anh_tiling_params tp = d::to_params(tiling_parameters);
+    NetPimpl::check(anh_infer_batch(net.handle(), b.images.data(), b.n, b.H, b.W, d::data_or_null(gains), d::data_or_null(detection_levels), &tp, b.results.data(),
+                                    temp.keep_blended_output ? b.planes_of.data() : nullptr));
+    if (temp.keep_blended_output) d::store_planes(temp, planes, K, b.H, b.W);
 }
 
 // What the reference's inference program does around annonet_infer() for a net trained with a downscaling factor, in one call on the
@@ -147,28 +150,18 @@ inline void annonet_infer_scaled(NetPimpl::RuntimeNet& net, const NetPimpl::inpu
                                  dlib::matrix<uint16_t>& result_image, annonet_infer_temp& temp, const std::vector<double>& gains = std::vector<double>(),
                                  const std::vector<double>& detection_levels = std::vector<double>(),
                                  const tiling::parameters& tiling_parameters = tiling::parameters()) {
-    anh_net_config cfg;
-    NetPimpl::check(anh_runtime_config(net.handle(), &cfg));
-    const int K = cfg.classes, H = (int)input_image.nr(), W = (int)input_image.nc();
-    if (!gains.empty() && (int)gains.size() != K) throw std::runtime_error("annonet_infer_scaled: one gain per class expected");
-    if (!detection_levels.empty() && (int)detection_levels.size() != K) throw std::runtime_error("annonet_infer_scaled: one detection level per class expected");
+    namespace d = annonet_infer_hip_detail;
+    const int K = d::classes_checked(net, "annonet_infer_scaled", gains, detection_levels), H = (int)input_image.nr(), W = (int)input_image.nc();
     int sh = 0, sw = 0;
     NetPimpl::check(anh_scaled_dims(H, W, downscaling_factor, &sh, &sw));
     result_image.set_size(H, W);
     temp.scaled_result_image.set_size(sh, sw);
     std::vector<float> planes;
     if (temp.keep_blended_output) planes.resize((size_t)K * sh * sw);
-    anh_tiling_params tp{tiling_parameters.max_tile_width, tiling_parameters.max_tile_height, tiling_parameters.overlap_x, tiling_parameters.overlap_y};
-    NetPimpl::check(anh_infer_scaled(net.handle(), reinterpret_cast<const uint8_t*>(&*input_image.begin()), H, W, downscaling_factor,
-                                     gains.empty() ? nullptr : gains.data(), detection_levels.empty() ? nullptr : detection_levels.data(), &tp,
+    const anh_tiling_params tp = d::to_params(tiling_parameters);
+    NetPimpl::check(anh_infer_scaled(net.handle(), d::pixels(input_image), H, W, downscaling_factor, d::data_or_null(gains), d::data_or_null(detection_levels), &tp,
                                      &*result_image.begin(), &*temp.scaled_result_image.begin(), temp.keep_blended_output ? planes.data() : nullptr));
-    if (temp.keep_blended_output) {
-        temp.blended_output.resize(K);
-        for (int k = 0; k < K; ++k) {
-            temp.blended_output[k].set_size(sh, sw);
-            std::copy(planes.begin() + (size_t)k * sh * sw, planes.begin() + (size_t)(k + 1) * sh * sw, temp.blended_output[k].begin());
-        }
-    }
+    if (temp.keep_blended_output) d::store_planes(temp, planes, K, sh, sw);
 }
 
 // annonet_infer_scaled() over several images of ONE original size in one call (anh_infer_scaled_batch): one batched shrink, the forward
@@ -180,40 +173,23 @@ inline void annonet_infer_scaled_batch(NetPimpl::RuntimeNet& net, const std::vec
                                        std::vector<dlib::matrix<uint16_t>>& result_images, annonet_infer_temp& temp,
                                        const std::vector<double>& gains = std::vector<double>(), const std::vector<double>& detection_levels = std::vector<double>(),
                                        const tiling::parameters& tiling_parameters = tiling::parameters()) {
-    anh_net_config cfg;
-    NetPimpl::check(anh_runtime_config(net.handle(), &cfg));
-    if (input_images.empty()) throw std::runtime_error("annonet_infer_scaled_batch: the batch needs at least one image");
-    const int K = cfg.classes, n = (int)input_images.size(), H = (int)input_images[0].nr(), W = (int)input_images[0].nc();
-    if (!gains.empty() && (int)gains.size() != K) throw std::runtime_error("annonet_infer_scaled_batch: one gain per class expected");
-    if (!detection_levels.empty() && (int)detection_levels.size() != K) throw std::runtime_error("annonet_infer_scaled_batch: one detection level per class expected");
+    namespace d = annonet_infer_hip_detail;
+    const int K = d::classes_checked(net, "annonet_infer_scaled_batch", gains, detection_levels, &input_images);
     int sh = 0, sw = 0;
-    NetPimpl::check(anh_scaled_dims(H, W, downscaling_factor, &sh, &sw));
-    std::vector<const uint8_t*> images((size_t)n);
-    std::vector<uint16_t*> results((size_t)n), scaled((size_t)n);
-    std::vector<float*> planes_of((size_t)n, nullptr);
-    result_images.resize((size_t)n);
-    temp.scaled_result_images.resize((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        if ((int)input_images[i].nr() != H || (int)input_images[i].nc() != W) throw std::runtime_error("annonet_infer_scaled_batch: the images of a batch must have one size");
-        images[i] = reinterpret_cast<const uint8_t*>(&*input_images[i].begin());
-        result_images[i].set_size(H, W);
-        results[i] = &*result_images[i].begin();
+    NetPimpl::check(anh_scaled_dims((int)input_images[0].nr(), (int)input_images[0].nc(), downscaling_factor, &sh, &sw));
+    d::batch_pointers b("annonet_infer_scaled_batch", input_images, result_images);
+    std::vector<uint16_t*> scaled((size_t)b.n);
+    temp.scaled_result_images.resize((size_t)b.n);
+    for (int i = 0; i < b.n; ++i) {
         temp.scaled_result_images[i].set_size(sh, sw);
         scaled[i] = &*temp.scaled_result_images[i].begin();
     }
     std::vector<float> planes;
-    if (temp.keep_blended_output) { planes.resize((size_t)K * sh * sw); planes_of[n - 1] = planes.data(); }
-    anh_tiling_params tp{tiling_parameters.max_tile_width, tiling_parameters.max_tile_height, tiling_parameters.overlap_x, tiling_parameters.overlap_y};
-    NetPimpl::check(anh_infer_scaled_batch(net.handle(), images.data(), n, H, W, downscaling_factor, gains.empty() ? nullptr : gains.data(),
-                                           detection_levels.empty() ? nullptr : detection_levels.data(), &tp, results.data(), scaled.data(),
-                                           temp.keep_blended_output ? planes_of.data() : nullptr));
-    if (temp.keep_blended_output) {
-        temp.blended_output.resize(K);
-        for (int k = 0; k < K; ++k) {
-            temp.blended_output[k].set_size(sh, sw);
-            std::copy(planes.begin() + (size_t)k * sh * sw, planes.begin() + (size_t)(k + 1) * sh * sw, temp.blended_output[k].begin());
-        }
-    }
+    if (temp.keep_blended_output) { planes.resize((size_t)K * sh * sw); b.planes_of[b.n - 1] = planes.data(); }
+    const anh_tiling_params tp = d::to_params(tiling_parameters);
+    NetPimpl::check(anh_infer_scaled_batch(net.handle(), b.images.data(), b.n, b.H, b.W, downscaling_factor, d::data_or_null(gains), d::data_or_null(detection_levels), &tp,
+                                           b.results.data(), scaled.data(), temp.keep_blended_output ? b.planes_of.data() : nullptr));
+    if (temp.keep_blended_output) d::store_planes(temp, planes, K, sh, sw);
 }
 
 #endif  // ANNONET_INFER_HIP_H
