@@ -143,6 +143,14 @@ _SIGNATURES = {  # ConvDesc / OpInput are defined above
     "anh_label_blobs_device": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(C.c_uint32)]),
     "anh_regions_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
     "anh_infer_regions": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), _P, _P, _P, C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
+    "anh_label_blobs_batch_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_uint32)]),
+    "anh_regions_batch_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
+    "anh_infer_regions_batch": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                          C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
+    "anh_infer_regions_scaled": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, _P, _P, C.POINTER(TilingParams), _P, _P, _P, _P,
+                                           C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
+    "anh_infer_regions_scaled_batch": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, C.POINTER(TilingParams), C.POINTER(_P), C.POINTER(_P),
+                                                 C.POINTER(_P), C.POINTER(_P), C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
     "anh_infer_device": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(TilingParams), C.POINTER(Tile), C.c_size_t, _P, _P]),
     "anh_infer_batch": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), C.POINTER(_P), C.POINTER(_P)]),
     "anh_infer_batch_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(TilingParams), _P, _P]),

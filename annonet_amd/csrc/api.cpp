@@ -622,7 +622,7 @@ void infer_streamed(anh_runtime* h, const uint8_t* image, int H, int W, const do
 
 namespace {
 // ---- one host-buffer inference call ----
-// What anh_infer, anh_infer_regions, anh_infer_batch, anh_infer_scaled and anh_infer_scaled_batch ask for, as ONE value: the entry
+// What anh_infer, anh_infer_batch, anh_infer_scaled, anh_infer_scaled_batch and the four anh_infer_regions forms ask for, as ONE value: the entry
 // points check their arguments and fill it, run_host_infer decides who serves it, run_share is the body that runs it.
 struct HostInfer {
     enum class Tail { none, filter, regions };
@@ -638,18 +638,21 @@ struct HostInfer {
     uint16_t* const* scaled = nullptr;    // ... the map of h x w and the planes [K][h][w]; either list and any entry may be null
     float* const* planes = nullptr;
     Tail tail = Tail::none;    // after the forward, at the net's resolution: the detection-level filter (some level is positive), or the region table
-    uint32_t* blobs = nullptr;            // Tail::regions (one image): the blob map (may be null), the malloc'd table
-    anh_region** regions = nullptr;
-    size_t* n_regions = nullptr;
+    uint32_t* const* blobs = nullptr;     // Tail::regions: per image the blob map of h x w (the list and any entry may be null), ...
+    anh_region** regions = nullptr;       // ... ONE malloc'd table for the images a share serves, the first image's rows first, ...
+    size_t* n_regions = nullptr;          // ... and per image the number of its rows
 
     bool resized() const { return factor != 1.0; }
     uint16_t* scaled_of(int i) const { return scaled ? scaled[i] : nullptr; }
     float* planes_of(int i) const { return planes ? planes[i] : nullptr; }
+    uint32_t* blobs_of(int i) const { return blobs ? blobs[i] : nullptr; }
     HostInfer single(int i) const {   // image i of a batch as the single-image call
         HostInfer c = *this;
         c.images += i; c.results += i;
         if (scaled) c.scaled += i;
         if (planes) c.planes += i;
+        if (blobs) c.blobs += i;
+        if (n_regions) c.n_regions += i;
         c.n = 1; c.batch = false;
         return c;
     }
@@ -755,7 +758,7 @@ void run_share(Engine& e, const HostInfer& c, int lo, int hi) {
     reserve_stage(e, (size_t)m, plane, planes);
     if (c.resized()) { e.stage_original.reserve((size_t)m * full * C); e.stage_upsampled.reserve((size_t)m * full * 2); }
     if (c.tail == Tail::filter) e.stage_out.reserve(detection_scratch_bytes(plane, K));
-    if (c.tail == Tail::regions) (void)e.reserve_blobs(c.h, c.w, K, true);
+    if (c.tail == Tail::regions) { if (c.batch) (void)e.reserve_blobs_batch(m, c.h, c.w, K, true); else (void)e.reserve_blobs(c.h, c.w, K, true); }
     if (c.batch) e.reserve_infer_batch(m, c.h, c.w, c.tiles, planes);   // the forward's own, ahead of the shrink
     uint8_t* d_image = e.stage_image.as<uint8_t>();
     float* d_planes = planes ? e.stage_blended.as<float>() : nullptr;
@@ -768,15 +771,14 @@ void run_share(Engine& e, const HostInfer& c, int lo, int hi) {
     else e.infer_device(d_image, c.h, c.w, c.gains, c.tiles, d_labels, d_planes, /*whole_image=*/true);
     // the tails run at the net's resolution, as the reference runs its filter before resize_label_image
     std::unique_ptr<anh_region, decltype(&std::free)> table(nullptr, &std::free);
-    size_t rows = 0;
     const uint32_t* d_blobs = nullptr;
-    for (int i = 0; i < m; ++i) {
-        if (c.tail == Tail::filter) apply_detection_levels(e, c.levels, K, c.h, c.w, d_planes + (size_t)i * K * plane, d_labels + (size_t)i * plane);
-        if (c.tail == Tail::regions) {   // (one image: the call has one table)
-            anh_region* t = nullptr;
-            d_blobs = e.regions(d_labels, d_planes, K, c.h, c.w, c.levels, /*filter=*/true, nullptr, &t, &rows);
-            table.reset(t);
-        }
+    if (c.tail == Tail::filter)
+        for (int i = 0; i < m; ++i) apply_detection_levels(e, c.levels, K, c.h, c.w, d_planes + (size_t)i * K * plane, d_labels + (size_t)i * plane);
+    if (c.tail == Tail::regions) {   // ONE call for the share's m maps: a single-image form keeps Engine::regions' launches
+        anh_region* t = nullptr;
+        if (c.batch) d_blobs = e.regions_batch(d_labels, d_planes, m, K, c.h, c.w, c.levels, /*filter=*/true, nullptr, &t, c.n_regions + lo);
+        else d_blobs = e.regions(d_labels, d_planes, K, c.h, c.w, c.levels, /*filter=*/true, nullptr, &t, c.n_regions + lo);
+        table.reset(t);
     }
     if (c.resized()) {
         e.resize_labels_batch(d_labels, m, c.h, c.w, e.stage_upsampled.as<uint16_t>(), c.H, c.W);
@@ -785,11 +787,11 @@ void run_share(Engine& e, const HostInfer& c, int lo, int hi) {
     for (int i = 0; i < m; ++i) {
         HIP_CHECK(hipMemcpyAsync(c.results[lo + i], d_results + (size_t)i * full, full * 2, hipMemcpyDeviceToHost, e.stream));
         if (c.resized() && c.scaled_of(lo + i)) HIP_CHECK(hipMemcpyAsync(c.scaled_of(lo + i), d_labels + (size_t)i * plane, plane * 2, hipMemcpyDeviceToHost, e.stream));
-        if (d_blobs && c.blobs) HIP_CHECK(hipMemcpyAsync(c.blobs, d_blobs, plane * 4, hipMemcpyDeviceToHost, e.stream));
+        if (d_blobs && c.blobs_of(lo + i)) HIP_CHECK(hipMemcpyAsync(c.blobs_of(lo + i), d_blobs + (size_t)i * plane, plane * 4, hipMemcpyDeviceToHost, e.stream));
         if (c.planes_of(lo + i)) HIP_CHECK(hipMemcpyAsync(c.planes_of(lo + i), d_planes + (size_t)i * K * plane, plane * K * 4, hipMemcpyDeviceToHost, e.stream));
     }
     e.synchronize();
-    if (c.tail == Tail::regions) { *c.regions = table.release(); *c.n_regions = rows; }
+    if (c.tail == Tail::regions) *c.regions = table.release();
 }
 
 // A single image, on replica 0 unless its tiles can be shared out.
@@ -815,13 +817,41 @@ void run_single(anh_runtime* h, const HostInfer& c) {
 void run_host_infer(anh_runtime* h, const HostInfer& c) {
     const size_t R = h->reps.size();
     if (!c.batch) run_single(h, c);
-    else if ((size_t)c.n < R) for (int i = 0; i < c.n; ++i) run_single(h, c.single(i));
-    else
-        h->reps.each([&](size_t r, Engine& e) {
-            int64_t lo = 0, hi = 0;
-            shard_range((int64_t)c.n, (int)R, (int)r, lo, hi);
-            if (hi > lo) run_share(e, c, (int)lo, (int)hi);
-        });
+    else {
+        // the shares in image order: image by image, or replica r's anh_shard_range
+        const bool by_image = (size_t)c.n < R;
+        std::vector<std::pair<int, int>> range(by_image ? (size_t)c.n : R);
+        for (size_t s = 0; s < range.size(); ++s) {
+            int64_t lo = (int64_t)s, hi = (int64_t)s + 1;
+            if (!by_image) shard_range((int64_t)c.n, (int)R, (int)s, lo, hi);
+            range[s] = {(int)lo, (int)hi};
+        }
+        // the region table: every share returns a table of its own; the call's ONE block is their concatenation in image order
+        const bool regions = c.tail == HostInfer::Tail::regions;
+        std::vector<anh_region*> part(range.size(), nullptr);
+        struct Release { std::vector<anh_region*>& p; ~Release() { for (anh_region* t : p) std::free(t); } } release{part};
+        auto share = [&](HostInfer s, size_t slot) { if (regions) s.regions = &part[slot]; return s; };
+        if (by_image) for (int i = 0; i < c.n; ++i) run_single(h, share(c.single(i), (size_t)i));
+        else
+            h->reps.each([&](size_t r, Engine& e) {
+                if (range[r].second > range[r].first) run_share(e, share(c, r), range[r].first, range[r].second);
+            });
+        if (regions && part.size() == 1) { *c.regions = part[0]; part[0] = nullptr; }
+        else if (regions) {
+            size_t rows = 0;
+            for (int i = 0; i < c.n; ++i) rows += c.n_regions[i];
+            anh_region* all = static_cast<anh_region*>(std::malloc(std::max<size_t>(1, rows * sizeof(anh_region))));
+            if (!all) fail(ANH_ERR_OOM, "host allocation of the region table failed");
+            size_t at = 0;
+            for (size_t s = 0; s < range.size(); ++s) {
+                size_t mine = 0;
+                for (int i = range[s].first; i < range[s].second; ++i) mine += c.n_regions[i];
+                if (mine) std::memcpy(all + at, part[s], mine * sizeof(anh_region));
+                at += mine;
+            }
+            *c.regions = all;
+        }
+    }
     if (!c.resized())
         for (int i = 0; i < c.n; ++i) if (c.scaled_of(i)) std::memcpy(c.scaled_of(i), c.results[i], (size_t)c.H * c.W * 2);
 }
@@ -871,8 +901,60 @@ int anh_infer_regions(anh_runtime* h, const uint8_t* image, int height, int widt
         ANH_REQUIRE(h && image && result && regions && n_regions, "null argument");
         HostInfer c(h, &image, 1, false, height, width, 1.0, height, width, gains, detection_levels, tiling, &result, nullptr, &blended_out);
         c.tail = HostInfer::Tail::regions;   // the blobs are those of the WHOLE label map: replica 0 alone, as anh_infer's filter
-        c.blobs = blobs; c.regions = regions; c.n_regions = n_regions;
+        c.blobs = &blobs; c.regions = regions; c.n_regions = n_regions;
         run_host_infer(h, c);
+    });
+}
+
+// ---- the same over n maps of one size (Engine::label_blobs_batch / regions_batch) ----
+namespace {
+void require_blob_batch_size(int n, int height, int width) {
+    ANH_REQUIRE(n >= 1, "the batch needs at least one image");
+    require_blob_map_size(height, width);
+    ANH_REQUIRE(blob_batch_fits(n, height, width), "blob labelling of a batch is limited to n * height * width (sides rounded up to 32) < 2^32 pixels");
+}
+void require_levels(const double* detection_levels, int classes) {
+    if (detection_levels) for (int k = 0; k < classes; ++k) ANH_REQUIRE(detection_levels[k] >= 0.0, "detection levels must be >= 0");
+}
+// what the three host-buffer forms share: the regions tail on a checked HostInfer
+void run_regions(anh_runtime* h, HostInfer c, uint32_t* const* blobs, anh_region** regions, size_t* n_regions) {
+    c.tail = HostInfer::Tail::regions;
+    c.blobs = blobs; c.regions = regions; c.n_regions = n_regions;
+    run_host_infer(h, c);
+}
+}  // namespace
+
+int anh_label_blobs_batch_device(anh_runtime* h, const uint16_t* d_labels, int n, int height, int width, uint32_t* d_blobs, uint32_t* counts) {
+    return guarded([&] {
+        require_blob_batch_size(n, height, width);   // first: a size beyond the limit is refused whatever else is wrong
+        ANH_REQUIRE(h && d_labels && d_blobs && counts, "null argument");
+        DeviceScope scope(h->reps.device_of(0));
+        h->reps.engine(0).label_blobs_batch(d_labels, n, height, width, d_blobs, counts);
+    });
+}
+
+int anh_regions_batch_device(anh_runtime* h, uint16_t* d_labels, const float* d_blended, int n, int classes, int height, int width, const double* detection_levels,
+                             int apply_filter, uint32_t* d_blobs, anh_region** regions, size_t* n_regions) {
+    return guarded([&] {
+        require_blob_batch_size(n, height, width);
+        ANH_REQUIRE(classes >= 1 && classes <= 65535, "regions: the class count must be within 1..65535");
+        require_levels(detection_levels, classes);
+        ANH_REQUIRE(h && d_labels && d_blended && regions && n_regions, "null argument");
+        DeviceScope scope(h->reps.device_of(0));
+        (void)h->reps.engine(0).regions_batch(d_labels, d_blended, n, classes, height, width, detection_levels, apply_filter != 0, d_blobs, regions, n_regions);
+    });
+}
+
+int anh_infer_regions_batch(anh_runtime* h, const uint8_t* const* images, int n, int height, int width, const double* gains, const double* detection_levels,
+                            const anh_tiling_params* tiling, uint16_t* const* results, uint32_t* const* blobs, float* const* blended_out, anh_region** regions,
+                            size_t* n_regions) {
+    return guarded([&] {
+        require_blob_batch_size(n, height, width);
+        ANH_REQUIRE(images && results, "infer_batch: null image or result list");
+        ANH_REQUIRE(h && regions && n_regions, "null argument");
+        for (int i = 0; i < n; ++i) ANH_REQUIRE(images[i] && results[i], "infer_batch: null image or result");
+        run_regions(h, HostInfer(h, images, n, true, height, width, 1.0, height, width, gains, detection_levels, tiling, results, nullptr, blended_out), blobs, regions,
+                    n_regions);
     });
 }
 
@@ -1062,6 +1144,36 @@ int anh_infer_scaled_batch(anh_runtime* h, const uint8_t* const* images, int n, 
         scaled_dims_checked(height, width, downscaling_factor, sh, sw);
         for (int i = 0; i < n; ++i) ANH_REQUIRE(images[i] && results[i], "infer_batch: null image or result");
         run_host_infer(h, HostInfer(h, images, n, true, height, width, downscaling_factor, sh, sw, gains, detection_levels, tiling, results, scaled_labels, blended_out));
+    });
+}
+
+// ---- regions of a downscaled call: the table and the blob map belong to the map at the net's resolution, the result map is blown up afterwards ----
+int anh_infer_regions_scaled(anh_runtime* h, const uint8_t* image, int height, int width, double downscaling_factor, const double* gains,
+                             const double* detection_levels, const anh_tiling_params* tiling, uint16_t* result, uint16_t* scaled_labels, uint32_t* blobs,
+                             float* blended_out, anh_region** regions, size_t* n_regions) {
+    return guarded([&] {
+        int sh = 0, sw = 0;
+        scaled_dims_checked(height, width, downscaling_factor, sh, sw);
+        require_blob_map_size(sh, sw);
+        ANH_REQUIRE(h && image && result && regions && n_regions, "null argument");
+        run_regions(h, HostInfer(h, &image, 1, false, height, width, downscaling_factor, sh, sw, gains, detection_levels, tiling, &result, &scaled_labels, &blended_out),
+                    &blobs, regions, n_regions);
+    });
+}
+
+int anh_infer_regions_scaled_batch(anh_runtime* h, const uint8_t* const* images, int n, int height, int width, double downscaling_factor, const double* gains,
+                                   const double* detection_levels, const anh_tiling_params* tiling, uint16_t* const* results, uint16_t* const* scaled_labels,
+                                   uint32_t* const* blobs, float* const* blended_out, anh_region** regions, size_t* n_regions) {
+    return guarded([&] {
+        ANH_REQUIRE(n >= 1, "infer_batch: the batch needs at least one image");
+        int sh = 0, sw = 0;
+        scaled_dims_checked(height, width, downscaling_factor, sh, sw);
+        require_blob_batch_size(n, sh, sw);
+        ANH_REQUIRE(images && results, "infer_batch: null image or result list");
+        ANH_REQUIRE(h && regions && n_regions, "null argument");
+        for (int i = 0; i < n; ++i) ANH_REQUIRE(images[i] && results[i], "infer_batch: null image or result");
+        run_regions(h, HostInfer(h, images, n, true, height, width, downscaling_factor, sh, sw, gains, detection_levels, tiling, results, scaled_labels, blended_out),
+                    blobs, regions, n_regions);
     });
 }
 

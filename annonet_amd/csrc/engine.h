@@ -189,6 +189,16 @@ class Engine {
     // blobs without a seed to 0 when a level is positive.  d_blobs may be null.  Returns the blob map it used.  Synchronises twice.
     uint32_t* regions(uint16_t* d_labels, const float* d_blended, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
                       anh_region** out, size_t* n);
+    // The same over n maps of one size lying back to back ([n][H][W], planes [n][K][H][W]), with launches that do not depend on n
+    // (kernels_blobs.hip, the `_batch_` kernels).  Scratch: [parents | block sums | counts | row offsets | levels | seed flags].
+    struct BlobBatchScratch { int* parent; unsigned* sums; unsigned* counts; unsigned long long* offsets; double* det; uint8_t* flags; };
+    BlobBatchScratch reserve_blobs_batch(int n, int H, int W, int K, bool own_map);
+    // counts: n host values, blobs + 1 each.  Synchronises once.
+    void label_blobs_batch(const uint16_t* d_labels, int n, int H, int W, uint32_t* d_blobs, uint32_t* counts);
+    // *out: ONE malloc'd block with image 0's rows, then image 1's, ...; n_regions: n host values; blob numbers restart at 1 per image.
+    // Synchronises twice whatever n is: for the counts (the host sums them into the row offsets) and for the table.
+    uint32_t* regions_batch(uint16_t* d_labels, const float* d_blended, int n, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
+                            anh_region** out, size_t* n_regions);
 
   private:
     void plan_dims(int n, int h, int w);

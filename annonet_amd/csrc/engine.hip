@@ -1298,4 +1298,80 @@ uint32_t* Engine::regions(uint16_t* d_labels, const float* d_blended, int K, int
     return d_blobs;
 }
 
+// ---- ... of n maps of one size lying back to back ----
+Engine::BlobBatchScratch Engine::reserve_blobs_batch(int n, int H, int W, int K, bool own_map) {
+    ANH_REQUIRE(n >= 1, "the stack needs at least one label map");
+    ANH_REQUIRE(H >= 1 && W >= 1, "empty label map");
+    ANH_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), "blob labelling is limited to height * width < 2^31 pixels");
+    ANH_REQUIRE(blob_batch_fits(n, H, W), "blob labelling of a stack is limited to n * height * width (sides rounded up to 32) < 2^32 pixels");
+    const size_t plane = (size_t)H * W, all = (size_t)n * plane;
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t sums_off = up(all * 4), counts_off = sums_off + up((size_t)n * blob_scan_blocks((int64_t)plane) * 4), offsets_off = counts_off + up((size_t)n * 4);
+    const size_t det_off = offsets_off + up((size_t)n * 8), flags_off = det_off + up((size_t)std::max(K, 1) * sizeof(double));
+    blob_scratch.reserve(flags_off + all);
+    if (own_map) blob_map.reserve(all * 4);
+    char* base = blob_scratch.as<char>();
+    return BlobBatchScratch{reinterpret_cast<int*>(base), reinterpret_cast<unsigned*>(base + sums_off), reinterpret_cast<unsigned*>(base + counts_off),
+                            reinterpret_cast<unsigned long long*>(base + offsets_off), reinterpret_cast<double*>(base + det_off),
+                            reinterpret_cast<uint8_t*>(base + flags_off)};
+}
+
+void Engine::label_blobs_batch(const uint16_t* d_labels, int n, int H, int W, uint32_t* d_blobs, uint32_t* counts) {
+    const BlobBatchScratch b = reserve_blobs_batch(n, H, W, 0, false);
+    const double px = (double)n * H * W;
+    const int tok = prof.begin(stream, "label_blobs_batch", 0, px * 40.0);
+    launch_blob_label_batch(d_labels, n, H, W, b.parent, d_blobs, b.sums, b.counts, stream);
+    launch_blob_number_batch(b.parent, d_blobs, d_labels, n, H, W, nullptr, nullptr, stream);
+    prof.end(stream, tok);
+    HIP_CHECK(hipMemcpyAsync(counts, b.counts, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    wait_stream(stream, bounded_waits);
+}
+
+uint32_t* Engine::regions_batch(uint16_t* d_labels, const float* d_blended, int n, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
+                                anh_region** out, size_t* n_regions) {
+    ANH_REQUIRE(K >= 1 && K <= 65535, "regions: the class count must be within 1..65535");
+    const BlobBatchScratch b = reserve_blobs_batch(n, H, W, K, d_blobs == nullptr);   // everything but the table, before the first kernel
+    if (!d_blobs) d_blobs = blob_map.as<uint32_t>();
+    bool positive = false;
+    std::vector<double> levels((size_t)K, 0.0);
+    if (levels_host) for (int k = 0; k < K; ++k) { ANH_REQUIRE(levels_host[k] >= 0.0, "detection levels must be >= 0"); positive = positive || levels_host[k] > 0.0; }
+    if (positive) levels.assign(levels_host, levels_host + K);
+    const double px = (double)n * H * W;
+    int tok = prof.begin(stream, "label_blobs_batch", 0, px * 40.0 + px * 11.0);
+    HIP_CHECK(hipMemcpyAsync(b.det, levels.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice, stream));
+    launch_detection_seeds_batch(d_blended, d_labels, K, n, H, W, b.det, b.flags, stream);
+    launch_blob_label_batch(d_labels, n, H, W, b.parent, d_blobs, b.sums, b.counts, stream);
+    prof.end(stream, tok);
+    std::vector<uint32_t> counts((size_t)n, 0);
+    HIP_CHECK(hipMemcpyAsync(counts.data(), b.counts, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    wait_stream(stream, bounded_waits);   // the first of the call's two waits: the counts size the table
+    std::vector<unsigned long long> offsets((size_t)n, 0);   // (read by the upload below, which the second wait covers)
+    unsigned long long total = 0;
+    for (int i = 0; i < n; ++i) {
+        ANH_REQUIRE(counts[(size_t)i] >= 1, "blob labelling returned no count");
+        offsets[(size_t)i] = total;
+        total += counts[(size_t)i] - 1;
+    }
+    if (total > 0xFFFFFFFFull) fail(ANH_ERR_OOM, "the region table of the stack would hold more than 2^32 rows");
+    const uint32_t rows = (uint32_t)total;
+    // the one reservation whose size is known only now; a failure leaves the handle as it was (the blob maps stay un-numbered)
+    if (rows) blob_table.reserve((size_t)rows * sizeof(anh_region));
+    anh_region* host = static_cast<anh_region*>(std::malloc(std::max<size_t>(1, (size_t)rows * sizeof(anh_region))));
+    if (!host) fail(ANH_ERR_OOM, "host allocation of the region table failed");
+    try {
+        anh_region* table = rows ? blob_table.as<anh_region>() : nullptr;
+        tok = prof.begin(stream, "blob_regions_batch", 0, px * 19.0);
+        HIP_CHECK(hipMemcpyAsync(b.offsets, offsets.data(), (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+        launch_blob_number_batch(b.parent, d_blobs, d_labels, n, H, W, table, b.offsets, stream);
+        launch_blob_stats_batch(d_blobs, d_labels, d_blended, K, n, H, W, b.flags, table, b.offsets, rows, positive, stream);
+        if (filter && positive && rows) launch_blob_filter_batch(d_labels, d_blobs, table, b.offsets, n, (int64_t)H * W, stream);
+        prof.end(stream, tok);
+        if (rows) HIP_CHECK(hipMemcpyAsync(host, table, (size_t)rows * sizeof(anh_region), hipMemcpyDeviceToHost, stream));
+        wait_stream(stream, bounded_waits);   // the second wait: the table
+    } catch (...) { std::free(host); throw; }
+    *out = host;
+    for (int i = 0; i < n; ++i) n_regions[i] = counts[(size_t)i] - 1;
+    return d_blobs;
+}
+
 }  // namespace anh

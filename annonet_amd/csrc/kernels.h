@@ -322,6 +322,22 @@ void launch_blob_stats(const uint32_t* d_blobs, const uint16_t* d_labels, const 
                        anh_region* d_table, uint32_t n_regions, bool filtering, hipStream_t s);
 // labels[p] = 0 where p's blob has no seed: one launch
 void launch_blob_filter(uint16_t* d_labels, const uint32_t* d_blobs, const anh_region* d_table, int64_t pixels, hipStream_t s);
+// ---- the same over n maps of one size lying back to back, [n][h][w]: the number of launches does not depend on n, and image i receives
+// exactly what the single-image launches give that map (blob numbers restart at 1 in every image) ----
+// what one launch can cover: h * w < 2^31 as above and n * (h and w rounded up to kBlobTile) < 2^32 pixels
+bool blob_batch_fits(int n, int h, int w);
+// flags [n][h][w] from d_blended [n][k][h][w] and d_labels [n][h][w]: launch_detection_seeds of every image, by one launch
+void launch_detection_seeds_batch(const float* d_blended, const uint16_t* d_labels, int k, int n, int h, int w, const double* d_det, uint8_t* d_flags, hipStream_t s);
+// d_sums: n * blob_scan_blocks(h * w) words; d_counts[i] = blobs of image i + 1.  d_parent, d_blobs: n * h * w words each.
+void launch_blob_label_batch(const uint16_t* d_labels, int n, int h, int w, int* d_parent, uint32_t* d_blobs, unsigned* d_sums, unsigned* d_counts, hipStream_t s);
+// d_row_offsets[i] = rows of the images before i (the host's exclusive sum of counts[i] - 1): image i's rows are d_table + d_row_offsets[i].
+// d_table == nullptr (then d_row_offsets is not read): the blob maps alone.
+void launch_blob_number_batch(const int* d_numbers, uint32_t* d_blobs, const uint16_t* d_labels, int n, int h, int w, anh_region* d_table,
+                              const unsigned long long* d_row_offsets, hipStream_t s);
+void launch_blob_stats_batch(const uint32_t* d_blobs, const uint16_t* d_labels, const float* d_blended, int k, int n, int h, int w, const uint8_t* d_flags,
+                             anh_region* d_table, const unsigned long long* d_row_offsets, uint32_t total_regions, bool filtering, hipStream_t s);
+void launch_blob_filter_batch(uint16_t* d_labels, const uint32_t* d_blobs, const anh_region* d_table, const unsigned long long* d_row_offsets, int n, int64_t pixels,
+                              hipStream_t s);
 void launch_reduce_partials(const float* partials, int splits, int64_t nw, float* out, hipStream_t s);
 
 struct BnFoldJobs;

@@ -1834,6 +1834,27 @@ __global__ __launch_bounds__(256) void det_seed_kernel(const float* blended, con
     }
 }
 
+// the same over images lying back to back: labels and flags [n][pixels], blended [n][k][pixels]; total = n * pixels
+__global__ __launch_bounds__(256) void det_seed_batch_kernel(const float* blended, const uint16_t* labels, int k, int64_t pixels, int64_t total, const double* det,
+                                                             uint8_t* flags, int transposed, int h, int w) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += stride) {
+        const int64_t image = q / pixels, p = q - image * pixels;
+        const float* planes = blended + (size_t)image * k * pixels;
+        const uint16_t lab = labels[q];
+        uint8_t f = 0;
+        if (lab != 0 && lab != ANH_LABEL_IGNORE && lab < k) {
+            const float clean = planes[p], mine = planes[(size_t)lab * pixels + p];
+            if ((double)(mine - clean) > det[lab] - det[0]) f = 1;
+        }
+        if (!transposed) flags[q] = f;
+        else if (f) {
+            const int64_t r = p / w, c = p - r * w;
+            if (c < h && r < w) flags[image * pixels + c * w + r] = 1;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void det_flood_kernel(const uint16_t* labels, uint8_t* flags, int h, int w, int* changed) {
     constexpr int T = 32, S = T + 2;
     __shared__ uint16_t lab[S][S];
@@ -1916,6 +1937,18 @@ void launch_detection_seeds(const float* d_blended, const uint16_t* d_labels, in
     static const int reference_order = getenv("ANH_DET_SEED_REFERENCE_ORDER") ? atoi(getenv("ANH_DET_SEED_REFERENCE_ORDER")) : 0;
     if (reference_order) HIP_CHECK(hipMemsetAsync(d_flags, 0, (size_t)pixels, s));
     hipLaunchKernelGGL(det_seed_kernel, dim3(blocks), dim3(256), 0, s, d_blended, d_labels, k, pixels, d_det, d_flags, reference_order, h, w);
+    HIP_CHECK(hipGetLastError());
+}
+
+// ... of n images lying back to back by ONE launch: every image's flags are those of launch_detection_seeds on that image alone (the
+// same float subtraction and double comparison per pixel; the transposed lookup stays inside the image's own plane)
+void launch_detection_seeds_batch(const float* d_blended, const uint16_t* d_labels, int k, int n, int h, int w, const double* d_det, uint8_t* d_flags, hipStream_t s) {
+    const int64_t pixels = (int64_t)h * w, total = pixels * n;
+    if (total == 0) return;
+    const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 16);
+    static const int reference_order = getenv("ANH_DET_SEED_REFERENCE_ORDER") ? atoi(getenv("ANH_DET_SEED_REFERENCE_ORDER")) : 0;
+    if (reference_order) HIP_CHECK(hipMemsetAsync(d_flags, 0, (size_t)total, s));
+    hipLaunchKernelGGL(det_seed_batch_kernel, dim3(blocks), dim3(256), 0, s, d_blended, d_labels, k, pixels, total, d_det, d_flags, reference_order, h, w);
     HIP_CHECK(hipGetLastError());
 }
 

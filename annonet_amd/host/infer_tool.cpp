@@ -49,7 +49,8 @@ const char* usage_text() {
            "      --host-resize                    downscaled nets: resize image and label map on the CPU threads, not on the GPU\n"
            "      --write-regions                  also write <image>_result_regions.csv: one line per DETECTED connected blob of the label map\n"
            "                                       (class_index,class_name,left,top,right,bottom,area,seeds,peak; boxes in pixels of the net's\n"
-           "                                       resolution).  Images go one by one, and a downscaled net takes the --host-resize route\n"
+           "                                       resolution).  Works with --image-batch and with the GPU resize of a downscaled net: the\n"
+           "                                       blobs of a whole batch are labelled together, at the net's resolution\n"
            "      --image-batch N                  up to N consecutive images of one size run as one batch (default: 1, image by image);\n"
            "                                       with a downscaled net whose resizes run on the GPU the batch forms on the ORIGINAL size and is\n"
            "                                       shrunk and blown up there by one launch each; with --devices the\n"
@@ -272,9 +273,9 @@ int run(const Settings& settings) {
     size_t labelled_pixels = 0;
     InferenceClock clock;
     annonet_infer_temp scratch;
-    // --write-regions: the table belongs to the map at the net's resolution, which annonet_infer_regions() computes on an image the readers
-    // have shrunk (the --host-resize route), image by image
-    const bool resize_on_gpu = trained.downscaling != 1.0 && !settings.host_resize && !settings.write_regions;
+    // --write-regions: the table belongs to the map at the net's resolution, whoever shrinks the image: the readers (--host-resize, then
+    // annonet_infer_regions() sees the shrunk image) or the GPU (annonet_infer_regions_scaled(), which labels before it blows the map up)
+    const bool resize_on_gpu = trained.downscaling != 1.0 && !settings.host_resize;
     {
         ImageReaders readers(files, settings.readers, trained.classes, trained.downscaling, !resize_on_gpu);
         ResultWriters writers(settings.writers, files.size(), trained.classes);
@@ -295,8 +296,9 @@ int run(const Settings& settings) {
         };
         // --image-batch N > 1: up to N consecutive samples of one size wait here and go through annonet_infer_batch() together; a sample
         // of another size flushes them first.  Where the GPU resizes (a factor other than 1 without --host-resize) the samples come at
-        // their ORIGINAL size, the groups form on it and go through annonet_infer_scaled_batch().
-        const bool batched = settings.image_batch > 1 && !settings.write_regions;
+        // their ORIGINAL size, the groups form on it and go through annonet_infer_scaled_batch().  --write-regions takes the same groups
+        // through the matching regions form, which labels the blobs of the whole group by one batched call.
+        const bool batched = settings.image_batch > 1;
         std::vector<sample_type> pending;
         auto flush = [&] {
             if (pending.empty()) return;
@@ -304,13 +306,17 @@ int run(const Settings& settings) {
             for (sample_type& s : pending) images.push_back(std::move(s.input_image));
             std::vector<dlib::matrix<uint16_t>> maps;
             const auto t0 = std::chrono::steady_clock::now();
-            if (resize_on_gpu) annonet_infer_scaled_batch(trained.net, images, trained.downscaling, maps, scratch, gains, detection_levels, tiles);
+            if (resize_on_gpu && settings.write_regions) annonet_infer_regions_scaled_batch(trained.net, images, trained.downscaling, maps, scratch, gains, detection_levels, tiles);
+            else if (resize_on_gpu) annonet_infer_scaled_batch(trained.net, images, trained.downscaling, maps, scratch, gains, detection_levels, tiles);
+            else if (settings.write_regions) annonet_infer_regions_batch(trained.net, images, maps, scratch, gains, detection_levels, tiles);
             else annonet_infer_batch(trained.net, images, maps, scratch, gains, detection_levels, tiles);
             clock.record_batch(std::chrono::duration_cast<InferenceClock::us>(std::chrono::steady_clock::now() - t0), pending.size());
             for (size_t j = 0; j < pending.size(); ++j) {
                 LabelMapToWrite result = result_for(pending[j]);
                 result.labels = std::move(maps[j]);
                 score(pending[j], resize_on_gpu ? scratch.scaled_result_images[j] : result.labels);
+                if (settings.write_regions)
+                    write_regions_csv(pending[j].image_filenames.image_filename + "_result_regions.csv", scratch.regions_per_image[j], trained.classes, trained.downscaling);
                 writers.submit(std::move(result));
             }
             pending.clear();
@@ -327,7 +333,8 @@ int run(const Settings& settings) {
             LabelMapToWrite result = result_for(sample);
 
             const auto t0 = std::chrono::steady_clock::now();
-            if (resize_on_gpu) annonet_infer_scaled(trained.net, sample.input_image, trained.downscaling, result.labels, scratch, gains, detection_levels, tiles);
+            if (resize_on_gpu && settings.write_regions) annonet_infer_regions_scaled(trained.net, sample.input_image, trained.downscaling, result.labels, scratch, gains, detection_levels, tiles);
+            else if (resize_on_gpu) annonet_infer_scaled(trained.net, sample.input_image, trained.downscaling, result.labels, scratch, gains, detection_levels, tiles);
             else if (settings.write_regions) annonet_infer_regions(trained.net, sample.input_image, result.labels, scratch, gains, detection_levels, tiles);
             else annonet_infer(trained.net, sample.input_image, result.labels, scratch, gains, detection_levels, tiles);
             clock.record(std::chrono::duration_cast<InferenceClock::us>(std::chrono::steady_clock::now() - t0));

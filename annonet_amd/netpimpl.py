@@ -664,6 +664,124 @@ def annonet_infer_regions(net, input_image, gains=None, detection_levels=None, t
     return tuple(out)
 
 
+def _take_regions_per_image(L, table, counts):
+    """the ONE malloc'd table of a batched regions call -> list of numpy structured arrays, one per image; releases the block"""
+    rows = _take_regions(L, table, int(sum(counts)))
+    ends = np.cumsum([0] + [int(c) for c in counts])
+    return [rows[ends[i]:ends[i + 1]] for i in range(len(counts))]
+
+
+def label_blobs_batch(label_maps, prefill=None, net=None):
+    """anh_label_blobs_batch_device on host u16 label maps [n,H,W]: (u32 blob maps [n,H,W], list of n counts, blobs + 1 each).  Blob
+    numbers restart at 1 in every image.  `prefill` as for label_blobs."""
+    a = np.require(label_maps, dtype=np.uint16, requirements=["C", "W"])
+    if a.ndim != 3 or a.shape[0] < 1:
+        raise AnnonetHipError(1, "label_blobs_batch: label maps [n,H,W] with n >= 1")
+    net = _net_for_blobs(net)
+    counts = (C.c_uint32 * a.shape[0])()
+
+    def launch(s, d, st):
+        import torch
+        torch.cuda.current_stream().synchronize()
+        check(net.L.anh_label_blobs_batch_device(net.h, s, a.shape[0], a.shape[1], a.shape[2], d, counts))
+    blobs = _through_device(a, a.shape, np.uint32, prefill, launch)
+    return blobs, list(counts)
+
+
+def regions_batch_device(net, d_labels_ptr, d_blended_ptr, n, classes, height, width, detection_levels=None, apply_filter=False, d_blobs_ptr=0):
+    """anh_regions_batch_device on resident buffers (device pointers as ints): the list of the n images' region tables."""
+    d = _f64(detection_levels)
+    if d is not None and d.size != classes:
+        raise AnnonetHipError(1, "detection levels need one value per class")
+    table, counts = C.POINTER(_lib.Region)(), (C.c_size_t * max(n, 1))()
+    check(net.L.anh_regions_batch_device(net.h, d_labels_ptr, d_blended_ptr, n, classes, height, width, _ptr(d), 1 if apply_filter else 0, d_blobs_ptr or None,
+                                         C.byref(table), counts))
+    return _take_regions_per_image(net.L, table, list(counts)[:n])
+
+
+def regions_batch(label_maps, blended, detection_levels=None, apply_filter=False, prefill=None, net=None):
+    """anh_regions_batch_device on host arrays (torch moves the bytes): u16 label maps [n,H,W] and fp32 planes [n,K,H,W] ->
+    (list of n region tables, u32 blob maps [n,H,W], the label maps as the call leaves them)."""
+    import torch
+    lab = np.require(label_maps, dtype=np.uint16, requirements=["C", "W"])
+    planes = np.require(blended, dtype=np.float32, requirements=["C", "W"])
+    if lab.ndim != 3 or lab.shape[0] < 1 or planes.ndim != 4 or planes.shape[:1] + planes.shape[2:] != lab.shape:
+        raise AnnonetHipError(1, "regions_batch: label maps [n,H,W] and planes [n,K,H,W]")
+    net = _net_for_blobs(net)
+    n, H, W = lab.shape
+    d_lab = torch.from_numpy(lab.view(np.uint8).reshape(-1)).cuda()
+    d_planes = torch.from_numpy(planes).cuda()
+    size = n * H * W * 4
+    d_blobs = torch.empty(size, dtype=torch.uint8, device="cuda") if prefill is None else torch.full((size,), int(prefill) & 255, dtype=torch.uint8, device="cuda")
+    torch.cuda.current_stream().synchronize()
+    tables = regions_batch_device(net, d_lab.data_ptr(), d_planes.data_ptr(), n, planes.shape[1], H, W, detection_levels, apply_filter, d_blobs.data_ptr())
+    return tables, d_blobs.cpu().numpy().view(np.uint32).reshape(n, H, W), d_lab.cpu().numpy().view(np.uint16).reshape(n, H, W)
+
+
+def _regions_outputs(out, tables, wanted):
+    """(results..., tables) followed by the optional lists that were asked for"""
+    return tuple(out) + (tables,) + tuple(arrays for want, arrays in wanted if want)
+
+
+def annonet_infer_regions_batch(net, input_images, gains=None, detection_levels=None, tiling_parameters=None, want_blobs=False, want_blended=False):
+    """annonet_infer_regions over several images of ONE size in one call (anh_infer_regions_batch): returns (list of label maps, list of
+    region tables), followed by the list of u32 blob maps and the list of blended planes when asked for.  want_blobs / want_blended may
+    also be lists of booleans, one per image (None where not asked for).  Every image's results equal annonet_infer_regions() of that
+    image alone, bit for bit."""
+    g, d = _per_class(net, gains, detection_levels)
+    imgs, H, W = _images(net, input_images)
+    n = len(imgs)
+    wb, wp = _per_image(want_blobs, n), _per_image(want_blended, n)
+    res = _outputs([True] * n, (H, W), np.uint16)
+    blobs = _outputs(wb, (H, W), np.uint32)
+    bl = _outputs(wp, (net.cfg.classes, H, W), np.float32)
+    table, counts = C.POINTER(_lib.Region)(), (C.c_size_t * max(n, 1))()
+    check(net.L.anh_infer_regions_batch(net.h, _ptrs(imgs, n), n, H, W, _ptr(g), _ptr(d), _tiling_ref(tiling_parameters), _ptrs(res, n),
+                                        _ptrs(blobs, n) if any(wb) else None, _ptrs(bl, n) if any(wp) else None, C.byref(table), counts))
+    tables = _take_regions_per_image(net.L, table, list(counts)[:n])
+    return _regions_outputs([res], tables, [(any(wb) or want_blobs, blobs), (any(wp) or want_blended, bl)])
+
+
+def annonet_infer_regions_scaled(net, input_image, downscaling_factor, gains=None, detection_levels=None, tiling_parameters=None, want_scaled=False, want_blobs=False,
+                                 want_blended=False):
+    """annonet_infer_scaled plus the region table of the unfiltered map at the net's resolution (anh_infer_regions_scaled): returns
+    (original-size label map, table), followed by the map, the u32 blob map and the blended planes at the net's resolution when asked for."""
+    (img,), H, W = _images(net, [input_image])
+    g, d = _per_class(net, gains, detection_levels)
+    sh, sw = scaled_dims(H, W, downscaling_factor)
+    res = np.empty((H, W), np.uint16)
+    scaled = np.empty((sh, sw), np.uint16) if want_scaled else None
+    blobs = np.empty((sh, sw), np.uint32) if want_blobs else None
+    bl = np.empty((net.cfg.classes, sh, sw), np.float32) if want_blended else None
+    table, n = C.POINTER(_lib.Region)(), C.c_size_t()
+    check(net.L.anh_infer_regions_scaled(net.h, _ptr(img), H, W, downscaling_factor, _ptr(g), _ptr(d), _tiling_ref(tiling_parameters), _ptr(res), _ptr(scaled),
+                                         _ptr(blobs), _ptr(bl), C.byref(table), C.byref(n)))
+    return _regions_outputs([res], _take_regions(net.L, table, n.value), [(want_scaled, scaled), (want_blobs, blobs), (want_blended, bl)])
+
+
+def annonet_infer_regions_scaled_batch(net, input_images, downscaling_factor, gains=None, detection_levels=None, tiling_parameters=None, want_scaled=False,
+                                       want_blobs=False, want_blended=False):
+    """annonet_infer_scaled_batch plus the region tables (anh_infer_regions_scaled_batch): returns (list of original-size label maps, list
+    of region tables), followed by the lists of maps, u32 blob maps and blended planes at the net's resolution when asked for.  The
+    want_* arguments may also be lists of booleans, one per image.  Every image's results equal annonet_infer_regions_scaled() of that
+    image alone, bit for bit."""
+    g, d = _per_class(net, gains, detection_levels)
+    imgs, H, W = _images(net, input_images)
+    n = len(imgs)
+    sh, sw = scaled_dims(H, W, downscaling_factor) if n else (0, 0)
+    ws, wb, wp = _per_image(want_scaled, n), _per_image(want_blobs, n), _per_image(want_blended, n)
+    res = _outputs([True] * n, (H, W), np.uint16)
+    sc = _outputs(ws, (sh, sw), np.uint16)
+    blobs = _outputs(wb, (sh, sw), np.uint32)
+    bl = _outputs(wp, (net.cfg.classes, sh, sw), np.float32)
+    table, counts = C.POINTER(_lib.Region)(), (C.c_size_t * max(n, 1))()
+    check(net.L.anh_infer_regions_scaled_batch(net.h, _ptrs(imgs, n), n, H, W, downscaling_factor, _ptr(g), _ptr(d), _tiling_ref(tiling_parameters), _ptrs(res, n),
+                                               _ptrs(sc, n) if any(ws) else None, _ptrs(blobs, n) if any(wb) else None, _ptrs(bl, n) if any(wp) else None,
+                                               C.byref(table), counts))
+    tables = _take_regions_per_image(net.L, table, list(counts)[:n])
+    return _regions_outputs([res], tables, [(any(ws) or want_scaled, sc), (any(wb) or want_blobs, blobs), (any(wp) or want_blended, bl)])
+
+
 def argmax_device(net, d_blended_ptr, height, width, row0, row1, d_labels_ptr, gains=None):
     """find_label (annonet_infer.cpp:170-185) over rows [row0, row1) of device-resident blended planes."""
     check(net.L.anh_argmax_device(net.h, d_blended_ptr, height, width, row0, row1, _ptr(_f64(gains)), d_labels_ptr))

@@ -263,6 +263,44 @@ int anh_regions_device(anh_runtime* h, uint16_t* d_labels, const float* d_blende
 int anh_infer_regions(anh_runtime* h, const uint8_t* image_hwc, int height, int width,
                       const double* gains, const double* detection_levels, const anh_tiling_params* tiling,
                       uint16_t* result_labels, uint32_t* blobs, float* blended_out, anh_region** regions, size_t* n_regions);
+/* ---- the same over n >= 1 label maps of ONE size lying back to back, with a number of launches that does not depend on n ----
+ * d_labels [n][height][width], d_blobs [n][height][width], d_blended [n][classes][height][width].  Every image is labelled on its own
+ * (no blob reaches from one image into the next) and its blob numbers restart at 1: image i gets, bit for bit, the blob map, the count
+ * and the rows the single-image calls give that map.  Limits: height * width < 2^31 as above, and n * height * width, with the sides
+ * rounded up to 32, < 2^32 pixels (ANH_ERR_INVALID beyond).
+ * counts: n host values, blobs + 1 each.  The call synchronises the stream once. */
+int anh_label_blobs_batch_device(anh_runtime* h, const uint16_t* d_labels, int n, int height, int width, uint32_t* d_blobs, uint32_t* counts);
+/* *regions is ONE malloc'd block (release with anh_free): image 0's rows, then image 1's, ...; n_regions: n host values, n_regions[i] =
+ * rows of image i; row.blob restarts at 1 per image.  d_blobs: NULL or [n][height][width].  Levels, `detected`, `peak`, apply_filter and
+ * ANH_DET_SEED_REFERENCE_ORDER as anh_regions_device documents them; the filter zeroes the blobs without a seed in all n maps by one
+ * launch.  The call waits on the host twice whatever n is: for the counts (the host sums them into the images' row offsets) and for the
+ * table.  Everything but the table is reserved before the first kernel; the table once the counts are known, and if that fails the call
+ * returns ANH_ERR_OOM and the handle stays usable. */
+int anh_regions_batch_device(anh_runtime* h, uint16_t* d_labels, const float* d_blended, int n, int classes, int height, int width,
+                             const double* detection_levels, int apply_filter, uint32_t* d_blobs /* NULL or [n][H][W] */,
+                             anh_region** regions, size_t* n_regions /* n host values */);
+/* anh_infer_batch plus the region tables of its UNFILTERED label maps, by ONE batched regions call per share.  results[i], blobs[i],
+ * blended_out[i] and image i's rows equal, bit for bit, what anh_infer_regions returns for image i alone.  blobs / blended_out: NULL, or
+ * n pointers of which each may be NULL.  *regions: ONE malloc'd block, image 0's rows first; n_regions: n host values.  On a handle with
+ * R replicas replica r serves the images anh_shard_range(n, R, r) and the host concatenates the shares' tables in image order; n < R
+ * goes image by image on replica 0, as anh_infer_regions does. */
+int anh_infer_regions_batch(anh_runtime* h, const uint8_t* const* images_hwc, int n, int height, int width,
+                            const double* gains, const double* detection_levels, const anh_tiling_params* tiling,
+                            uint16_t* const* results, uint32_t* const* blobs, float* const* blended_out, anh_region** regions, size_t* n_regions);
+/* anh_infer_scaled plus the region table: table and blob map belong to the map at the net's resolution (anh_scaled_dims), where the
+ * reference runs its filter; the result map is blown up afterwards.  What comes back equals anh_infer_regions of the shrunk image (and
+ * the nearest-neighbour blow-up of its map); labels and planes equal anh_infer_scaled's.  Factor 1.0 is exactly anh_infer_regions.
+ * scaled_labels, blobs, blended_out: optional (NULL), at the net's resolution. */
+int anh_infer_regions_scaled(anh_runtime* h, const uint8_t* image_hwc, int height, int width, double downscaling_factor,
+                             const double* gains, const double* detection_levels, const anh_tiling_params* tiling,
+                             uint16_t* result_labels, uint16_t* scaled_labels, uint32_t* blobs, float* blended_out, anh_region** regions, size_t* n_regions);
+/* anh_infer_scaled_batch plus the region tables: one batched shrink, the forward batches, ONE batched regions call at the net's
+ * resolution, one batched blow-up.  Image i equals anh_infer_regions_scaled of image i alone; scaled_labels / blobs / blended_out: NULL,
+ * or n pointers of which each may be NULL.  Factor 1.0 is exactly anh_infer_regions_batch.  Replicas as for anh_infer_regions_batch. */
+int anh_infer_regions_scaled_batch(anh_runtime* h, const uint8_t* const* images_hwc, int n, int height, int width, double downscaling_factor,
+                                   const double* gains, const double* detection_levels, const anh_tiling_params* tiling,
+                                   uint16_t* const* results, uint16_t* const* scaled_labels, uint32_t* const* blobs, float* const* blended_out,
+                                   anh_region** regions, size_t* n_regions);
 /* label rows [row0, row1) of device-resident blended planes (find_label, annonet_infer.cpp:170-185): the second half of a
    sharded annonet_infer(), run after the ranks have exchanged the plane sums of their overlapping tiles */
 int anh_argmax_device(anh_runtime* h, const float* d_blended, int height, int width, int row0, int row1, const double* gains, uint16_t* d_result);

@@ -36,6 +36,9 @@ struct annonet_infer_temp {  // annonet_infer.h:26-32; the GPU path keeps its sc
     // detection_seeds stays empty: it can be as long as the image, and regions[i].seeds carries the count per blob.
     std::vector<anh_region> regions;
     bool keep_connected_blobs = false;
+    // annonet_infer_regions_batch / _scaled_batch: image i's table (blob numbers restart at 1 per image) and, under keep_connected_blobs, its blob map
+    std::vector<std::vector<anh_region>> regions_per_image;
+    std::vector<dlib::matrix<unsigned int>> connected_blobs_per_image;
 };
 
 namespace annonet_infer_hip_detail {
@@ -189,6 +192,114 @@ inline void annonet_infer_scaled_batch(NetPimpl::RuntimeNet& net, const std::vec
     const anh_tiling_params tp = d::to_params(tiling_parameters);
     NetPimpl::check(anh_infer_scaled_batch(net.handle(), b.images.data(), b.n, b.H, b.W, downscaling_factor, d::data_or_null(gains), d::data_or_null(detection_levels), &tp,
                                            b.results.data(), scaled.data(), temp.keep_blended_output ? b.planes_of.data() : nullptr));
+    if (temp.keep_blended_output) d::store_planes(temp, planes, K, sh, sw);
+}
+
+namespace annonet_infer_hip_detail {
+// what the batched regions forms share: the blob maps (when kept) sized to h x w, and the call's ONE table cut into temp.regions_per_image
+inline std::vector<uint32_t*> blob_pointers(annonet_infer_temp& temp, int n, int h, int w) {
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "connected_blobs receives the u32 blob map as it is");
+    std::vector<uint32_t*> blobs((size_t)n, nullptr);
+    temp.connected_blobs_per_image.resize(temp.keep_connected_blobs ? (size_t)n : 0);
+    for (int i = 0; i < n && temp.keep_connected_blobs; ++i) {
+        temp.connected_blobs_per_image[i].set_size(h, w);
+        blobs[i] = reinterpret_cast<uint32_t*>(&*temp.connected_blobs_per_image[i].begin());
+    }
+    return blobs;
+}
+inline void store_regions_per_image(annonet_infer_temp& temp, anh_region* table, const std::vector<size_t>& rows) {
+    try {
+        temp.regions_per_image.resize(rows.size());
+        const anh_region* at = table;
+        for (size_t i = 0; i < rows.size(); ++i) { temp.regions_per_image[i].assign(at, at + rows[i]); at += rows[i]; }
+    } catch (...) { anh_free(table); throw; }
+    anh_free(table);
+}
+}  // namespace annonet_infer_hip_detail
+
+// annonet_infer_regions() over several images of ONE size in one call (anh_infer_regions_batch): the forward batches of
+// annonet_infer_batch(), then ONE batched labelling of all the maps.  result_images[i], temp.regions_per_image[i] and (under
+// keep_connected_blobs) temp.connected_blobs_per_image[i] belong to input_images[i] and equal, bit for bit, what annonet_infer_regions()
+// gives for that image alone.  temp.blended_output holds the planes of the LAST image, as after annonet_infer_batch().
+inline void annonet_infer_regions_batch(NetPimpl::RuntimeNet& net, const std::vector<NetPimpl::input_type>& input_images,
+                                        std::vector<dlib::matrix<uint16_t>>& result_images, annonet_infer_temp& temp,
+                                        const std::vector<double>& gains = std::vector<double>(), const std::vector<double>& detection_levels = std::vector<double>(),
+                                        const tiling::parameters& tiling_parameters = tiling::parameters()) {
+    namespace d = annonet_infer_hip_detail;
+    const int K = d::classes_checked(net, "annonet_infer_regions_batch", gains, detection_levels, &input_images);
+    d::batch_pointers b("annonet_infer_regions_batch", input_images, result_images);
+    std::vector<uint32_t*> blobs = d::blob_pointers(temp, b.n, b.H, b.W);
+    std::vector<float> planes;
+    if (temp.keep_blended_output) { planes.resize((size_t)K * b.H * b.W); b.planes_of[b.n - 1] = planes.data(); }
+    const anh_tiling_params tp = d::to_params(tiling_parameters);
+    anh_region* table = nullptr;
+    std::vector<size_t> rows((size_t)b.n, 0);
+    NetPimpl::check(anh_infer_regions_batch(net.handle(), b.images.data(), b.n, b.H, b.W, d::data_or_null(gains), d::data_or_null(detection_levels), &tp, b.results.data(),
+                                            temp.keep_connected_blobs ? blobs.data() : nullptr, temp.keep_blended_output ? b.planes_of.data() : nullptr, &table,
+                                            rows.data()));
+    d::store_regions_per_image(temp, table, rows);
+    if (temp.keep_blended_output) d::store_planes(temp, planes, K, b.H, b.W);
+}
+
+// annonet_infer_scaled() plus the region table (anh_infer_regions_scaled): temp.regions and (under keep_connected_blobs)
+// temp.connected_blobs belong to temp.scaled_result_image's unfiltered map, at the net's resolution, where the reference runs its filter;
+// result_image is that map, filtered, blown up to the original size.
+inline void annonet_infer_regions_scaled(NetPimpl::RuntimeNet& net, const NetPimpl::input_type& input_image, double downscaling_factor,
+                                         dlib::matrix<uint16_t>& result_image, annonet_infer_temp& temp, const std::vector<double>& gains = std::vector<double>(),
+                                         const std::vector<double>& detection_levels = std::vector<double>(),
+                                         const tiling::parameters& tiling_parameters = tiling::parameters()) {
+    namespace d = annonet_infer_hip_detail;
+    const int K = d::classes_checked(net, "annonet_infer_regions_scaled", gains, detection_levels), H = (int)input_image.nr(), W = (int)input_image.nc();
+    int sh = 0, sw = 0;
+    NetPimpl::check(anh_scaled_dims(H, W, downscaling_factor, &sh, &sw));
+    result_image.set_size(H, W);
+    temp.scaled_result_image.set_size(sh, sw);
+    if (temp.keep_connected_blobs) temp.connected_blobs.set_size(sh, sw);
+    std::vector<float> planes;
+    if (temp.keep_blended_output) planes.resize((size_t)K * sh * sw);
+    const anh_tiling_params tp = d::to_params(tiling_parameters);
+    anh_region* table = nullptr;
+    size_t rows = 0;
+    NetPimpl::check(anh_infer_regions_scaled(net.handle(), d::pixels(input_image), H, W, downscaling_factor, d::data_or_null(gains), d::data_or_null(detection_levels), &tp,
+                                             &*result_image.begin(), &*temp.scaled_result_image.begin(),
+                                             temp.keep_connected_blobs ? reinterpret_cast<uint32_t*>(&*temp.connected_blobs.begin()) : nullptr,
+                                             temp.keep_blended_output ? planes.data() : nullptr, &table, &rows));
+    try { temp.regions.assign(table, table + rows); } catch (...) { anh_free(table); throw; }
+    anh_free(table);
+    if (temp.keep_blended_output) d::store_planes(temp, planes, K, sh, sw);
+}
+
+// annonet_infer_regions_scaled() over several images of ONE original size in one call (anh_infer_regions_scaled_batch): one batched
+// shrink, the forward batches, ONE batched labelling at the net's resolution, one batched blow-up.  Fills result_images,
+// temp.scaled_result_images, temp.regions_per_image and (under keep_connected_blobs) temp.connected_blobs_per_image, image by image as
+// annonet_infer_regions_scaled() gives them.
+inline void annonet_infer_regions_scaled_batch(NetPimpl::RuntimeNet& net, const std::vector<NetPimpl::input_type>& input_images, double downscaling_factor,
+                                               std::vector<dlib::matrix<uint16_t>>& result_images, annonet_infer_temp& temp,
+                                               const std::vector<double>& gains = std::vector<double>(),
+                                               const std::vector<double>& detection_levels = std::vector<double>(),
+                                               const tiling::parameters& tiling_parameters = tiling::parameters()) {
+    namespace d = annonet_infer_hip_detail;
+    const int K = d::classes_checked(net, "annonet_infer_regions_scaled_batch", gains, detection_levels, &input_images);
+    int sh = 0, sw = 0;
+    NetPimpl::check(anh_scaled_dims((int)input_images[0].nr(), (int)input_images[0].nc(), downscaling_factor, &sh, &sw));
+    d::batch_pointers b("annonet_infer_regions_scaled_batch", input_images, result_images);
+    std::vector<uint16_t*> scaled((size_t)b.n);
+    temp.scaled_result_images.resize((size_t)b.n);
+    for (int i = 0; i < b.n; ++i) {
+        temp.scaled_result_images[i].set_size(sh, sw);
+        scaled[i] = &*temp.scaled_result_images[i].begin();
+    }
+    std::vector<uint32_t*> blobs = d::blob_pointers(temp, b.n, sh, sw);
+    std::vector<float> planes;
+    if (temp.keep_blended_output) { planes.resize((size_t)K * sh * sw); b.planes_of[b.n - 1] = planes.data(); }
+    const anh_tiling_params tp = d::to_params(tiling_parameters);
+    anh_region* table = nullptr;
+    std::vector<size_t> rows((size_t)b.n, 0);
+    NetPimpl::check(anh_infer_regions_scaled_batch(net.handle(), b.images.data(), b.n, b.H, b.W, downscaling_factor, d::data_or_null(gains),
+                                                   d::data_or_null(detection_levels), &tp, b.results.data(), scaled.data(),
+                                                   temp.keep_connected_blobs ? blobs.data() : nullptr, temp.keep_blended_output ? b.planes_of.data() : nullptr, &table,
+                                                   rows.data()));
+    d::store_regions_per_image(temp, table, rows);
     if (temp.keep_blended_output) d::store_planes(temp, planes, K, sh, sw);
 }
 
