@@ -142,6 +142,7 @@ _SIGNATURES = {  # ConvDesc / OpInput are defined above
     "anh_infer": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), _P, _P]),
     "anh_label_blobs_device": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(C.c_uint32)]),
     "anh_regions_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
+    "anh_detection_filter_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
     "anh_infer_regions": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), _P, _P, _P, C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
     "anh_label_blobs_batch_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_uint32)]),
     "anh_regions_batch_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),

@@ -290,13 +290,14 @@ bool detection_requested(const double* detection_levels, int K) {
 // Seeds are looked up at (row, col): the reference stores (r, c) but reads (point.y(), point.x()) — transposed (:210 vs :222); see DESIGN.md.
 // Its scratch, e.stage_out of detection_scratch_bytes, is the caller's to reserve (with the rest, before its first kernel).
 size_t detection_scratch_bytes(size_t plane, int K) { return plane + (size_t)K * sizeof(double) + 64; }   // flags, levels, the change counter
-void apply_detection_levels(Engine& e, const double* levels, int K, int h, int w, const float* d_blended, uint16_t* d_labels) {
+// Returns run_detection_filter's host rounds.
+int apply_detection_levels(Engine& e, const double* levels, int K, int h, int w, const float* d_blended, uint16_t* d_labels) {
     const size_t plane = (size_t)h * w;
     uint8_t* flags = e.stage_out.as<uint8_t>();
     double* d_det = reinterpret_cast<double*>(flags + ((plane + 15) / 16) * 16);
     int* d_changed = reinterpret_cast<int*>(d_det + K);
     HIP_CHECK(hipMemcpyAsync(d_det, levels, (size_t)K * sizeof(double), hipMemcpyHostToDevice, e.stream));
-    run_detection_filter(d_blended, d_labels, K, h, w, d_det, flags, d_changed, e.stream);
+    return run_detection_filter(d_blended, d_labels, K, h, w, d_det, flags, d_changed, e.stream);
 }
 // stage_image / stage_result for n images of `plane` pixels, and stage_blended for their class planes where a path blends into them
 void reserve_stage(Engine& e, size_t n, size_t plane, bool planes = true) {
@@ -773,7 +774,7 @@ void run_share(Engine& e, const HostInfer& c, int lo, int hi) {
     std::unique_ptr<anh_region, decltype(&std::free)> table(nullptr, &std::free);
     const uint32_t* d_blobs = nullptr;
     if (c.tail == Tail::filter)
-        for (int i = 0; i < m; ++i) apply_detection_levels(e, c.levels, K, c.h, c.w, d_planes + (size_t)i * K * plane, d_labels + (size_t)i * plane);
+        for (int i = 0; i < m; ++i) (void)apply_detection_levels(e, c.levels, K, c.h, c.w, d_planes + (size_t)i * K * plane, d_labels + (size_t)i * plane);
     if (c.tail == Tail::regions) {   // ONE call for the share's m maps: a single-image form keeps Engine::regions' launches
         anh_region* t = nullptr;
         if (c.batch) d_blobs = e.regions_batch(d_labels, d_planes, m, K, c.h, c.w, c.levels, /*filter=*/true, nullptr, &t, c.n_regions + lo);
@@ -891,6 +892,24 @@ int anh_regions_device(anh_runtime* h, uint16_t* d_labels, const float* d_blende
         ANH_REQUIRE(h && d_labels && d_blended && regions && n_regions, "null argument");
         DeviceScope scope(h->reps.device_of(0));
         (void)h->reps.engine(0).regions(d_labels, d_blended, classes, height, width, detection_levels, apply_filter != 0, d_blobs, regions, n_regions);
+    });
+}
+
+// the detection-level filter of anh_infer alone, on a resident map: Tail::filter's rule and its apply_detection_levels
+int anh_detection_filter_device(anh_runtime* h, uint16_t* d_labels, const float* d_blended, int classes, int height, int width, const double* detection_levels,
+                                int* rounds) {
+    return guarded([&] {
+        ANH_REQUIRE(h && d_labels && d_blended, "null argument");
+        ANH_REQUIRE(classes >= 1 && classes <= 65535, "detection filter: the class count must be within 1..65535");
+        ANH_REQUIRE(height >= 1 && width >= 1, "empty label map");
+        if (rounds) *rounds = 0;
+        if (!detection_requested(detection_levels, classes)) return;   // no positive level: nothing is ever removed
+        DeviceScope scope(h->reps.device_of(0));
+        Engine& e = h->reps.engine(0);
+        e.stage_out.reserve(detection_scratch_bytes((size_t)height * width, classes));
+        const int made = apply_detection_levels(e, detection_levels, classes, height, width, d_blended, d_labels);
+        e.synchronize();   // the apply launch: the map is final when the call returns
+        if (rounds) *rounds = made;
     });
 }
 

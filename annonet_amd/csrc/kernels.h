@@ -302,8 +302,9 @@ void launch_crop_pixels(const CropSource* d_specs, int n, int dim, int channels,
                         unsigned* d_hist, unsigned* d_firstpos, int* d_bad_label, int classes, hipStream_t s);
 // pass 2: weights[p] = table[crop][label] (0 for ignored pixels); table from set_weights' arithmetic on the histograms
 void launch_crop_weights(const uint16_t* d_labels, const float* d_table, int n, int dim, float* d_weights, hipStream_t s);
-// detection-level filter of annonet_infer() on the device (kernels_generic.hip)
-void run_detection_filter(const float* d_blended, uint16_t* d_labels, int k, int h, int w, const double* d_det, uint8_t* d_flags, int* d_changed,
+// detection-level filter of annonet_infer() on the device (kernels_generic.hip); returns the host rounds it made (4 flood launches and one
+// read-back each; the last one is the quiet round that ends the loop)
+int run_detection_filter(const float* d_blended, uint16_t* d_labels, int k, int h, int w, const double* d_det, uint8_t* d_flags, int* d_changed,
                           hipStream_t s);
 // the filter's first launch on its own: flags[p] = 1 where pixel p is a detection seed (ANH_DET_SEED_REFERENCE_ORDER honoured); H*W bytes
 void launch_detection_seeds(const float* d_blended, const uint16_t* d_labels, int k, int h, int w, const double* d_det, uint8_t* d_flags, hipStream_t s);

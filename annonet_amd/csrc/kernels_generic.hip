@@ -1905,15 +1905,17 @@ __global__ __launch_bounds__(256) void det_apply_kernel(uint16_t* labels, const 
 }  // namespace
 
 // Relabels every blob without a seed to 0, in place.  d_flags: H*W bytes of scratch; d_changed: one int; det: K doubles on the device.
-void run_detection_filter(const float* d_blended, uint16_t* d_labels, int k, int h, int w, const double* d_det, uint8_t* d_flags, int* d_changed,
+// Returns the number of host rounds made, the quiet last one included.
+int run_detection_filter(const float* d_blended, uint16_t* d_labels, int k, int h, int w, const double* d_det, uint8_t* d_flags, int* d_changed,
                           hipStream_t s) {
     const int64_t pixels = (int64_t)h * w;
-    if (pixels == 0) return;
+    if (pixels == 0) return 0;
     const int blocks = (int)std::min<int64_t>((pixels + 255) / 256, 256 * 16);
     static const int reference_order = getenv("ANH_DET_SEED_REFERENCE_ORDER") ? atoi(getenv("ANH_DET_SEED_REFERENCE_ORDER")) : 0;
     if (reference_order) HIP_CHECK(hipMemsetAsync(d_flags, 0, (size_t)pixels, s));
     hipLaunchKernelGGL(det_seed_kernel, dim3(blocks), dim3(256), 0, s, d_blended, d_labels, k, pixels, d_det, d_flags, reference_order, h, w);
     HIP_CHECK(hipGetLastError());
+    int rounds = 0;
     const dim3 grid((unsigned)((w + 31) / 32), (unsigned)((h + 31) / 32));
     for (int round = 0;; ++round) {
         ANH_REQUIRE(round < 100000, "detection filter did not converge");
@@ -1923,10 +1925,12 @@ void run_detection_filter(const float* d_blended, uint16_t* d_labels, int k, int
         int changed = 0;
         HIP_CHECK(hipMemcpyAsync(&changed, d_changed, sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
+        rounds = round + 1;
         if (!changed) break;
     }
     hipLaunchKernelGGL(det_apply_kernel, dim3(blocks), dim3(256), 0, s, d_labels, d_flags, pixels);
     HIP_CHECK(hipGetLastError());
+    return rounds;
 }
 
 // The seed launch of run_detection_filter on its own (the region table counts these flags per blob, kernels_blobs.hip).

@@ -645,6 +645,42 @@ def regions(label_map, blended, detection_levels=None, apply_filter=False, prefi
     return table, d_blobs.cpu().numpy().view(np.uint32).reshape(H, W), d_lab.cpu().numpy().view(np.uint16).reshape(H, W)
 
 
+def detection_filter_device(net, d_labels_ptr, d_blended_ptr, classes, height, width, detection_levels):
+    """anh_detection_filter_device on resident buffers (device pointers as ints): annonet_infer's flood filter on the map, in place;
+    returns the host rounds it made (0 when no level is positive: the map is untouched)."""
+    d = _f64(detection_levels)
+    if d is not None and d.size != classes:
+        raise AnnonetHipError(1, "detection levels need one value per class")
+    rounds = C.c_int(-1)
+    check(net.L.anh_detection_filter_device(net.h, d_labels_ptr or None, d_blended_ptr or None, classes, height, width, _ptr(d), C.byref(rounds)))
+    return rounds.value
+
+
+def detection_filter(label_map, blended, detection_levels, net=None, prefill_scratch=None):
+    """anh_detection_filter_device on host arrays (torch moves the bytes): u16 label map [H,W] and fp32 planes [K,H,W] ->
+    (the filtered map, host rounds).  `prefill_scratch` (tests: the filter must not read what an earlier call left): a shape (h, w), or
+    True for the map's own; the handle first filters a throwaway map of that shape in which every pixel is a seed, which leaves every
+    flag byte of the scratch it covers at 1."""
+    import torch
+    lab = np.require(label_map, dtype=np.uint16, requirements=["C", "W"])
+    planes = np.require(blended, dtype=np.float32, requirements=["C", "W"])
+    if lab.ndim != 2 or planes.ndim != 3 or planes.shape[1:] != lab.shape:
+        raise AnnonetHipError(1, "detection_filter: a label map [H,W] and planes [K,H,W]")
+    net = _net_for_blobs(net)
+    H, W = lab.shape
+    if prefill_scratch is not None and prefill_scratch is not False:
+        h, w = (H, W) if prefill_scratch is True else prefill_scratch
+        d_ones = torch.ones(h * w, dtype=torch.int16, device="cuda")           # label 1 everywhere, margin 0 > -1: all seeds
+        d_zero = torch.zeros(2 * h * w, dtype=torch.float32, device="cuda")
+        torch.cuda.current_stream().synchronize()
+        detection_filter_device(net, d_ones.data_ptr(), d_zero.data_ptr(), 2, h, w, [1.0, 0.0])
+    d_lab = torch.from_numpy(lab.view(np.uint8).reshape(-1)).cuda()
+    d_planes = torch.from_numpy(planes).cuda()
+    torch.cuda.current_stream().synchronize()
+    rounds = detection_filter_device(net, d_lab.data_ptr(), d_planes.data_ptr(), planes.shape[0], H, W, detection_levels)
+    return d_lab.cpu().numpy().view(np.uint16).reshape(H, W), rounds
+
+
 def annonet_infer_regions(net, input_image, gains=None, detection_levels=None, tiling_parameters=None, want_blobs=False, want_blended=False):
     """annonet_infer() plus the region table of its unfiltered label map (anh_infer_regions): returns (label map, table as a numpy
     structured array of REGION_DTYPE), followed by the u32 blob map and the blended planes when asked for."""

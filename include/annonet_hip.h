@@ -257,6 +257,13 @@ int anh_label_blobs_device(anh_runtime* h, const uint16_t* d_labels, int height,
  * first kernel; the table is reserved once the count is known, and if that fails the call returns ANH_ERR_OOM and the handle stays usable. */
 int anh_regions_device(anh_runtime* h, uint16_t* d_labels, const float* d_blended, int classes, int height, int width,
                        const double* detection_levels, int apply_filter, uint32_t* d_blobs, anh_region** regions, size_t* n_regions);
+/* The detection-level filter of anh_infer alone, on a resident label map [height][width] and its `classes` planes, in place: the flood
+ * launches every anh_infer form with a positive level runs (not the one-launch filter of the regions calls; both leave the same map).
+ * detection_levels: `classes` host doubles or NULL.  No positive level: the map is left untouched and *rounds = 0.  Otherwise every blob
+ * without a seed becomes 0 and *rounds (NULL allowed) receives the host rounds made, the quiet last one included.  The call waits for
+ * the stream: the map is final when it returns. */
+int anh_detection_filter_device(anh_runtime* h, uint16_t* d_labels, const float* d_blended, int classes, int height, int width,
+                                const double* detection_levels, int* rounds /* nullable */);
 /* anh_infer plus the region table of its UNFILTERED label map (annonet_infer.cpp:217 labels before :229-238 filter): result_labels and
  * blended_out are bit-identical to what anh_infer returns for the same arguments on one device.  blobs: NULL, or height * width u32 on
  * the host. */

@@ -8,70 +8,11 @@ from scipy import ndimage
 
 import annonet_amd as aa
 import blobs_ref as br
+from blobs_ref import PATTERNS, SIZES, T, pattern, smooth_map
 
 pytestmark = pytest.mark.gpu
 
-T = 32          # kBlobTile (annonet_amd/csrc/kernels.h)
 K = 3
-SIZES = [(1, 1), (1, 2 * T + 6), (2 * T + 6, 1), (T - 1, T + 1), (T + 1, T - 1), (2 * T, 2 * T), (3 * T + 1, 4 * T + 2)]
-
-
-def spiral(h, w):
-    """a one-pixel path that winds inwards from (0, 0) and leaves one pixel of background between its turns: ONE blob, one long chain"""
-    a = np.zeros((h, w), np.uint16)
-    y = x = 0
-    dy, dx = 0, 1
-    a[0, 0] = 1
-    failed = 0
-    while failed < 2:
-        ny, nx, fy, fx = y + dy, x + dx, y + 2 * dy, x + 2 * dx
-        ahead_free = not (0 <= fy < h and 0 <= fx < w) or a[fy, fx] == 0
-        if 0 <= ny < h and 0 <= nx < w and a[ny, nx] == 0 and ahead_free:
-            y, x = ny, nx
-            a[y, x] = 1
-            failed = 0
-        else:
-            dy, dx = dx, -dy
-            failed += 1
-    return a
-
-
-def pattern(name, shape):
-    h, w = shape
-    rng = np.random.default_rng(h * 1000 + w)
-    if name == "random":
-        return rng.integers(0, 3, shape).astype(np.uint16)
-    if name == "random_wide_values":
-        return rng.choice(np.array([0, 1, 2, 7, 65535], np.uint16), size=shape, p=[0.3, 0.25, 0.25, 0.1, 0.1])
-    if name == "checkerboard":          # every colour is ONE blob through its diagonals
-        yy, xx = np.mgrid[0:h, 0:w]
-        return (1 + (yy + xx) % 2).astype(np.uint16)
-    if name == "corner_diagonals":      # (T-1,T-1)->(T,T) and (T-1,T)->(T,T-1): pairs that touch only across the corner where four tiles meet
-        a = np.zeros(shape, np.uint16)
-        for (y, x, v) in ((T - 1, T - 1, 1), (T, T, 1), (T - 1, T, 2), (T, T - 1, 2)):
-            if y < h and x < w:
-                a[y, x] = v
-        for i in range(min(h, w)):       # and a long diagonal of a third label through every tile corner on its way
-            if a[i, i] == 0 and i not in (T - 1, T):
-                a[i, i] = 3
-        return a
-    if name == "spiral":
-        return spiral(h, w)
-    if name == "full":
-        return np.full(shape, 2, np.uint16)
-    if name == "u_shape":               # arms in different tile columns that meet only in the last row: the root moves to the earlier arm's first pixel
-        a = np.zeros(shape, np.uint16)
-        left, right = min(3, w - 1), max(w - 3, 0)
-        a[min(5, h - 1):, right] = 1     # the right arm starts higher up ...
-        a[min(9, h - 1):, left] = 1      # ... than the left one
-        a[h - 1, left:right + 1] = 1
-        return a
-    if name == "zeros":
-        return np.zeros(shape, np.uint16)
-    raise KeyError(name)
-
-
-PATTERNS = ["random", "random_wide_values", "checkerboard", "corner_diagonals", "spiral", "full", "u_shape", "zeros"]
 _cache = {}
 
 
@@ -87,18 +28,6 @@ def case(name, shape):
         planes.setflags(write=False)
         _cache[key] = (lab, planes) + br.region_table(lab, planes)
     return _cache[key]
-
-
-def smooth_map(shape, seed):
-    rng = np.random.default_rng(seed)
-    field = ndimage.gaussian_filter(rng.normal(size=shape), 6.0)
-    other = ndimage.gaussian_filter(rng.normal(size=shape), 9.0)
-    lab = np.zeros(shape, np.uint16)
-    s = field.std()
-    lab[field > 0.4 * s] = 1
-    lab[field < -0.5 * s] = 2
-    lab[(other > 1.2 * other.std()) & (lab == 0)] = 65535
-    return lab
 
 
 @pytest.mark.parametrize("shape", SIZES, ids=lambda s: "%dx%d" % s)
