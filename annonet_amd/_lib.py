@@ -152,6 +152,10 @@ _SIGNATURES = {  # ConvDesc / OpInput are defined above
                                            C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
     "anh_infer_regions_scaled_batch": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, C.POINTER(TilingParams), C.POINTER(_P), C.POINTER(_P),
                                                  C.POINTER(_P), C.POINTER(_P), C.POINTER(C.POINTER(Region)), C.POINTER(C.c_size_t)]),
+    "anh_score_batch_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "anh_score_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "anh_score_batch": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "anh_score": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "anh_infer_device": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(TilingParams), C.POINTER(Tile), C.c_size_t, _P, _P]),
     "anh_infer_batch": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), C.POINTER(_P), C.POINTER(_P)]),
     "anh_infer_batch_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(TilingParams), _P, _P]),

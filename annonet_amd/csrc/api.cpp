@@ -977,6 +977,64 @@ int anh_infer_regions_batch(anh_runtime* h, const uint8_t* const* images, int n,
     });
 }
 
+// ---- scoring result maps against their ground truth (Engine::score_stacked) ----
+namespace {
+void require_score_sizes(int n, int classes, int height, int width) {
+    ANH_REQUIRE(n >= 1, "score: the batch needs at least one image");
+    ANH_REQUIRE(classes >= 1 && classes <= 65535, "score: the class count must be within 1..65535");
+    require_blob_map_size(height, width);
+    // truth and result maps are labelled together, as one stack of 2n maps
+    ANH_REQUIRE(n < (1 << 30) && blob_batch_fits(2 * n, height, width), "scoring a batch is limited to 2 * n * height * width (sides rounded up to 32) < 2^32 pixels");
+}
+// the maps go into the engine's stack [truth maps ; result maps]: by n copies each from host pointers, by one copy each from resident stacks
+void run_score(anh_runtime* h, const uint16_t* const* truth, const uint16_t* const* result, const uint16_t* d_truth, const uint16_t* d_result, int n, int classes,
+               int height, int width, uint64_t* per_pixel, uint64_t* per_region, uint64_t* labelled) {
+    DeviceScope scope(h->reps.device_of(0));
+    Engine& e = h->reps.engine(0);
+    uint16_t* stack = e.reserve_score(n, classes, height, width);   // everything but the vote table, before anything is enqueued
+    const size_t plane = (size_t)height * width, bytes = plane * sizeof(uint16_t);
+    if (d_truth) {
+        HIP_CHECK(hipMemcpyAsync(stack, d_truth, bytes * n, hipMemcpyDeviceToDevice, e.stream));
+        HIP_CHECK(hipMemcpyAsync(stack + plane * n, d_result, bytes * n, hipMemcpyDeviceToDevice, e.stream));
+    } else {
+        for (int i = 0; i < n; ++i) {
+            HIP_CHECK(hipMemcpyAsync(stack + plane * i, truth[i], bytes, hipMemcpyHostToDevice, e.stream));
+            HIP_CHECK(hipMemcpyAsync(stack + plane * ((size_t)n + i), result[i], bytes, hipMemcpyHostToDevice, e.stream));
+        }
+    }
+    e.score_stacked(n, classes, height, width, per_pixel, per_region, labelled);
+}
+}  // namespace
+
+int anh_score_batch_device(anh_runtime* h, const uint16_t* d_truth, const uint16_t* d_result, int n, int classes, int height, int width, uint64_t* per_pixel,
+                           uint64_t* per_region, uint64_t* labelled) {
+    return guarded([&] {
+        require_score_sizes(n, classes, height, width);   // first: a size beyond the limit is refused whatever else is wrong
+        ANH_REQUIRE(h && d_truth && d_result, "null argument");
+        run_score(h, nullptr, nullptr, d_truth, d_result, n, classes, height, width, per_pixel, per_region, labelled);
+    });
+}
+
+int anh_score_device(anh_runtime* h, const uint16_t* d_truth, const uint16_t* d_result, int classes, int height, int width, uint64_t* per_pixel, uint64_t* per_region,
+                     uint64_t* labelled) {
+    return anh_score_batch_device(h, d_truth, d_result, 1, classes, height, width, per_pixel, per_region, labelled);
+}
+
+int anh_score_batch(anh_runtime* h, const uint16_t* const* truth, const uint16_t* const* result, int n, int classes, int height, int width, uint64_t* per_pixel,
+                    uint64_t* per_region, uint64_t* labelled) {
+    return guarded([&] {
+        require_score_sizes(n, classes, height, width);
+        ANH_REQUIRE(h && truth && result, "null argument");
+        for (int i = 0; i < n; ++i) ANH_REQUIRE(truth[i] && result[i], "score: null map");
+        run_score(h, truth, result, nullptr, nullptr, n, classes, height, width, per_pixel, per_region, labelled);
+    });
+}
+
+int anh_score(anh_runtime* h, const uint16_t* truth, const uint16_t* result, int classes, int height, int width, uint64_t* per_pixel, uint64_t* per_region,
+              uint64_t* labelled) {
+    return anh_score_batch(h, &truth, &result, 1, classes, height, width, per_pixel, per_region, labelled);
+}
+
 // ---- annonet_infer() over several images of one size (Engine::infer_batch_device) ----
 int anh_infer_batch_device(anh_runtime* h, const uint8_t* d_images, int n, int height, int width, const double* gains, const anh_tiling_params* tiling,
                            uint16_t* d_results, float* d_blended) {

@@ -200,6 +200,17 @@ class Engine {
     uint32_t* regions_batch(uint16_t* d_labels, const float* d_blended, int n, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
                             anh_region** out, size_t* n_regions);
 
+    // ---- scoring result maps against their ground truth (kernels_score.hip; annonet_infer_main.cpp:482-491, RegionScorer) ----
+    // Everything a score call of n pairs of H x W maps with K classes needs but the vote table, reserved before anything is enqueued.
+    // Returns the stack [2n][H][W] the caller copies the maps into: the n truth maps, then the n result maps.
+    uint16_t* reserve_score(int n, int K, int H, int W);
+    DevBuf score_maps, score_votes, score_out;
+    std::vector<uint64_t> host_score;   // score_out as it comes back
+    // the counts of the stack reserve_score returned: per_pixel, per_region [n][K][K], labelled [n], host u64, each may be null.  ONE batched
+    // labelling of the 2n maps, the tally, the decide launch.  Synchronises twice whatever n is: for the counts (they size the vote
+    // table) and for the matrices.
+    void score_stacked(int n, int K, int H, int W, uint64_t* per_pixel, uint64_t* per_region, uint64_t* labelled);
+
   private:
     void plan_dims(int n, int h, int w);
     void plan_dims_unguarded(int n, int h, int w);

@@ -1374,4 +1374,51 @@ uint32_t* Engine::regions_batch(uint16_t* d_labels, const float* d_blended, int 
     return d_blobs;
 }
 
+// ---- scoring result maps against their ground truth ----
+uint16_t* Engine::reserve_score(int n, int K, int H, int W) {
+    ANH_REQUIRE(n >= 1, "score: the batch needs at least one pair of maps");
+    ANH_REQUIRE(K >= 1 && K <= 65535, "score: the class count must be within 1..65535");
+    (void)reserve_blobs_batch(2 * n, H, W, 0, true);   // the labeller's scratch and the 2n blob maps (checks the sizes)
+    const size_t plane = (size_t)H * W, cells = (size_t)n * K * K;
+    score_maps.reserve(2 * (size_t)n * plane * sizeof(uint16_t));
+    score_out.reserve(((size_t)n + 2 * cells) * sizeof(uint64_t));   // [labelled | per pixel | per region]
+    host_score.resize((size_t)n + 2 * cells);
+    return score_maps.as<uint16_t>();
+}
+
+void Engine::score_stacked(int n, int K, int H, int W, uint64_t* per_pixel, uint64_t* per_region, uint64_t* labelled) {
+    const uint16_t* maps = reserve_score(n, K, H, W);   // (the caller reserved already: nothing moves)
+    uint32_t* blobs = blob_map.as<uint32_t>();
+    std::vector<uint32_t> counts((size_t)(2 * n), 0);
+    label_blobs_batch(maps, 2 * n, H, W, blobs, counts.data());   // the first of the call's two waits
+    std::vector<unsigned long long> offsets((size_t)(2 * n), 0);   // (read by the upload below, which the second wait covers)
+    unsigned long long total = 0;
+    for (int i = 0; i < 2 * n; ++i) {
+        ANH_REQUIRE(counts[(size_t)i] >= 1, "blob labelling returned no count");
+        offsets[(size_t)i] = total;
+        total += counts[(size_t)i];   // blobs + 1: the map's regions, region 0 included
+    }
+    if (total > 0xFFFFFFFFull) fail(ANH_ERR_OOM, "the vote table of the stack would hold more than 2^32 rows");
+    const uint32_t rows = (uint32_t)total;
+    // the one reservation whose size is known only now; a failure leaves the handle as it was
+    const size_t vote_bytes = (size_t)rows * ((size_t)K + 1) * sizeof(unsigned);
+    score_votes.reserve(vote_bytes);
+    const BlobBatchScratch b = reserve_blobs_batch(2 * n, H, W, 0, true);
+    const size_t cells = (size_t)n * K * K, out_words = (size_t)n + 2 * cells;
+    unsigned long long* out = score_out.as<unsigned long long>();
+    const double px = (double)n * H * W;
+    const int tok = prof.begin(stream, "score_batch", 0, px * 12.0 + 2.0 * (double)vote_bytes);
+    HIP_CHECK(hipMemcpyAsync(b.offsets, offsets.data(), offsets.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemsetAsync(score_votes.p, 0, vote_bytes, stream));
+    HIP_CHECK(hipMemsetAsync(out, 0, out_words * sizeof(uint64_t), stream));
+    launch_score_tally(maps, blobs, n, K, H, W, b.offsets, score_votes.as<unsigned>(), out, out + n, stream);
+    launch_score_decide(score_votes.as<unsigned>(), b.offsets, n, K, rows, out + n + cells, stream);
+    prof.end(stream, tok);
+    HIP_CHECK(hipMemcpyAsync(host_score.data(), out, out_words * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    wait_stream(stream, bounded_waits);   // the second wait: the matrices
+    if (labelled) std::copy(host_score.begin(), host_score.begin() + n, labelled);
+    if (per_pixel) std::copy(host_score.begin() + n, host_score.begin() + n + (ptrdiff_t)cells, per_pixel);
+    if (per_region) std::copy(host_score.begin() + n + (ptrdiff_t)cells, host_score.end(), per_region);
+}
+
 }  // namespace anh

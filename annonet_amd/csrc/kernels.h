@@ -339,6 +339,14 @@ void launch_blob_stats_batch(const uint32_t* d_blobs, const uint16_t* d_labels, 
                              anh_region* d_table, const unsigned long long* d_row_offsets, uint32_t total_regions, bool filtering, hipStream_t s);
 void launch_blob_filter_batch(uint16_t* d_labels, const uint32_t* d_blobs, const anh_region* d_table, const unsigned long long* d_row_offsets, int n, int64_t pixels,
                               hipStream_t s);
+// ---- scoring result maps against their ground truth (kernels_score.hip; annonet_infer_main.cpp:482-491, :202-272) ----
+// d_maps [2n][h][w] = [n truth maps ; n result maps] and d_blobs their blob maps (launch_blob_label_batch + launch_blob_number_batch);
+// d_row_offsets: 2n values, the first vote row of every map (the host's exclusive sum of the labeller's counts: blobs + 1 = regions);
+// d_votes: one row of k + 1 words per region, CLEARED by the caller, as d_labelled [n] and d_pixel [n][k][k] are.  Integer atomics only.
+void launch_score_tally(const uint16_t* d_maps, const uint32_t* d_blobs, int n, int k, int h, int w, const unsigned long long* d_row_offsets, unsigned* d_votes,
+                        unsigned long long* d_labelled, unsigned long long* d_pixel, hipStream_t s);
+// one thread per vote row: d_region [n][k][k] (cleared by the caller) receives the regions' votes
+void launch_score_decide(const unsigned* d_votes, const unsigned long long* d_row_offsets, int n, int k, uint32_t rows, unsigned long long* d_region, hipStream_t s);
 void launch_reduce_partials(const float* partials, int splits, int64_t nw, float* out, hipStream_t s);
 
 struct BnFoldJobs;

@@ -13,6 +13,7 @@
 // shrinks it, infers and blows the label map back up there (the reference does both resizes on the CPU: annonet.cpp:153 in the readers,
 // annonet_infer_main.cpp:413 in the writers); --host-resize keeps them on this program's reader / writer threads.  Same files, same matrices.
 // --write-regions: annonet_infer_regions() instead of annonet_infer(), and <image>_result_regions.csv beside every result PNG.
+// --gpu-score: both confusion matrices are counted on the GPU by annonet_score(), not on this thread; the printed matrices are the same.
 #define ANNONET_HIP_NO_DLIB
 #include "../../include/annonet_infer_hip.h"
 #include "annonet_host.h"
@@ -30,6 +31,7 @@ struct Settings {
     int max_tile_w = 1024, max_tile_h = 1024;   // the reference's GPU-build defaults (:300-303)
     bool host_resize = false;
     bool write_regions = false;
+    bool gpu_score = false;
     int image_batch = 1;
     int readers = (int)std::max(1u, std::thread::hardware_concurrency()), writers = (int)std::max(1u, std::thread::hardware_concurrency());
 };
@@ -51,6 +53,8 @@ const char* usage_text() {
            "                                       (class_index,class_name,left,top,right,bottom,area,seeds,peak; boxes in pixels of the net's\n"
            "                                       resolution).  Works with --image-batch and with the GPU resize of a downscaled net: the\n"
            "                                       blobs of a whole batch are labelled together, at the net's resolution\n"
+           "      --gpu-score                      score the results against the masks on the GPU (annonet_score(): the blobs of truth and result\n"
+           "                                       maps are labelled there, a group of --image-batch images by one call); same matrices\n"
            "      --image-batch N                  up to N consecutive images of one size run as one batch (default: 1, image by image);\n"
            "                                       with a downscaled net whose resizes run on the GPU the batch forms on the ORIGINAL size and is\n"
            "                                       shrunk and blown up there by one launch each; with --devices the\n"
@@ -80,6 +84,7 @@ Settings read_command_line(int argc, char** argv) {
             option->second(argv[++i]);
         } else if (word == "--host-resize") s.host_resize = true;
         else if (word == "--write-regions") s.write_regions = true;
+        else if (word == "--gpu-score") s.gpu_score = true;
         else if (!word.empty() && word[0] == '-') throw std::runtime_error("Option '" + word + "' does not exist");
         else if (s.directory.empty()) s.directory = word;
         else throw std::runtime_error("Unexpected argument " + word);
@@ -288,6 +293,30 @@ int run(const Settings& settings) {
             }
             region_scorer.score(per_region, sample, scored);
         };
+        // --gpu-score: the same counts by ONE annonet_score() call over the samples that have a mask (the host scorer returns early for the
+        // others); truth = the sample's label_image, result = the map `score` would be handed, both at the net's resolution
+        const int class_count = (int)trained.classes.size();
+        annonet_score_counts counted;
+        auto score_on_gpu = [&](const std::vector<const sample_type*>& samples, const std::vector<const dlib::matrix<uint16_t>*>& scored) {
+            std::vector<const dlib::matrix<uint16_t>*> truth_maps, result_maps;
+            for (size_t j = 0; j < samples.size(); ++j) {
+                if (samples[j]->labeled_points_by_class.empty()) continue;
+                if (samples[j]->label_image.nr() != scored[j]->nr() || samples[j]->label_image.nc() != scored[j]->nc()) throw std::runtime_error("ground truth and result sizes differ");
+                truth_maps.push_back(&samples[j]->label_image);
+                result_maps.push_back(scored[j]);
+            }
+            if (truth_maps.empty()) return;
+            annonet_score(trained.net, truth_maps, result_maps, class_count, counted);
+            const size_t k = (size_t)class_count;
+            for (size_t i = 0; i < truth_maps.size(); ++i) {
+                for (size_t t = 0; t < k; ++t)
+                    for (size_t p = 0; p < k; ++p) {
+                        per_pixel.add(t, p, (size_t)counted.per_pixel[(i * k + t) * k + p]);
+                        per_region.add(t, p, (size_t)counted.per_region[(i * k + t) * k + p]);
+                    }
+                labelled_pixels += (size_t)counted.labelled[i];
+            }
+        };
         auto result_for = [](const sample_type& sample) {
             LabelMapToWrite result;
             result.path = sample.image_filenames.image_filename + "_result.png";
@@ -311,10 +340,16 @@ int run(const Settings& settings) {
             else if (settings.write_regions) annonet_infer_regions_batch(trained.net, images, maps, scratch, gains, detection_levels, tiles);
             else annonet_infer_batch(trained.net, images, maps, scratch, gains, detection_levels, tiles);
             clock.record_batch(std::chrono::duration_cast<InferenceClock::us>(std::chrono::steady_clock::now() - t0), pending.size());
+            if (settings.gpu_score) {
+                std::vector<const sample_type*> samples;
+                std::vector<const dlib::matrix<uint16_t>*> scored;
+                for (size_t j = 0; j < pending.size(); ++j) { samples.push_back(&pending[j]); scored.push_back(resize_on_gpu ? &scratch.scaled_result_images[j] : &maps[j]); }
+                score_on_gpu(samples, scored);
+            }
             for (size_t j = 0; j < pending.size(); ++j) {
                 LabelMapToWrite result = result_for(pending[j]);
                 result.labels = std::move(maps[j]);
-                score(pending[j], resize_on_gpu ? scratch.scaled_result_images[j] : result.labels);
+                if (!settings.gpu_score) score(pending[j], resize_on_gpu ? scratch.scaled_result_images[j] : result.labels);
                 if (settings.write_regions)
                     write_regions_csv(pending[j].image_filenames.image_filename + "_result_regions.csv", scratch.regions_per_image[j], trained.classes, trained.downscaling);
                 writers.submit(std::move(result));
@@ -338,7 +373,8 @@ int run(const Settings& settings) {
             else if (settings.write_regions) annonet_infer_regions(trained.net, sample.input_image, result.labels, scratch, gains, detection_levels, tiles);
             else annonet_infer(trained.net, sample.input_image, result.labels, scratch, gains, detection_levels, tiles);
             clock.record(std::chrono::duration_cast<InferenceClock::us>(std::chrono::steady_clock::now() - t0));
-            score(sample, resize_on_gpu ? scratch.scaled_result_image : result.labels);
+            if (settings.gpu_score) score_on_gpu({&sample}, {resize_on_gpu ? &scratch.scaled_result_image : &result.labels});
+            else score(sample, resize_on_gpu ? scratch.scaled_result_image : result.labels);
             if (settings.write_regions) write_regions_csv(sample.image_filenames.image_filename + "_result_regions.csv", scratch.regions, trained.classes, trained.downscaling);
             writers.submit(std::move(result));
         }

@@ -754,6 +754,56 @@ def regions_batch(label_maps, blended, detection_levels=None, apply_filter=False
     return tables, d_blobs.cpu().numpy().view(np.uint32).reshape(n, H, W), d_lab.cpu().numpy().view(np.uint16).reshape(n, H, W)
 
 
+def _score_outputs(n, classes, prefill):
+    """per_pixel, per_region [n,K,K] and labelled [n], u64; `prefill`: byte they are filled with before the call (tests: every
+    element must be overwritten)"""
+    shapes = ((n, classes, classes), (n, classes, classes), (n,))
+    if prefill is None:
+        return [np.empty(s, np.uint64) for s in shapes]
+    return [np.full(int(np.prod(s)) * 8, int(prefill) & 255, np.uint8).view(np.uint64).reshape(s) for s in shapes]
+
+
+def score_batch_device(net, d_truth_ptr, d_result_ptr, n, classes, height, width, prefill=None):
+    """anh_score_batch_device on resident u16 maps [n,H,W] (device pointers as ints), on the handle's stream: (per_pixel [n,K,K],
+    per_region [n,K,K], labelled [n]) as u64 arrays, first index ground truth."""
+    out = _score_outputs(max(n, 0), max(classes, 0), prefill)
+    check(net.L.anh_score_batch_device(net.h, d_truth_ptr or None, d_result_ptr or None, n, classes, height, width, *[_ptr(a) for a in out]))
+    return tuple(out)
+
+
+def score_device(net, d_truth_ptr, d_result_ptr, classes, height, width, prefill=None):
+    """anh_score_device on one resident pair of maps: (per_pixel [K,K], per_region [K,K], labelled)."""
+    pp, pr, lab = _score_outputs(1, max(classes, 0), prefill)
+    check(net.L.anh_score_device(net.h, d_truth_ptr or None, d_result_ptr or None, classes, height, width, _ptr(pp), _ptr(pr), _ptr(lab)))
+    return pp[0], pr[0], int(lab[0])
+
+
+def score_batch(truth_maps, result_maps, classes, prefill=None, net=None):
+    """anh_score_batch on host u16 maps [n,H,W] (the library uploads them): (per_pixel [n,K,K], per_region [n,K,K], labelled [n]).
+    `net`: the handle whose stream the call runs on (default: a smallest net of the module's own; scoring uses no weights)."""
+    t = np.ascontiguousarray(truth_maps, dtype=np.uint16)
+    r = np.ascontiguousarray(result_maps, dtype=np.uint16)
+    if t.ndim != 3 or t.shape[0] < 1 or r.shape != t.shape:
+        raise AnnonetHipError(1, "score_batch: truth and result maps [n,H,W] of one shape with n >= 1")
+    net = _net_for_blobs(net)
+    n = t.shape[0]
+    out = _score_outputs(n, max(classes, 0), prefill)
+    check(net.L.anh_score_batch(net.h, _ptrs(list(t), n), _ptrs(list(r), n), n, classes, t.shape[1], t.shape[2], *[_ptr(a) for a in out]))
+    return tuple(out)
+
+
+def score(truth_map, result_map, classes, prefill=None, net=None):
+    """anh_score on one host pair of u16 maps [H,W]: (per_pixel [K,K], per_region [K,K], labelled)."""
+    t = np.ascontiguousarray(truth_map, dtype=np.uint16)
+    r = np.ascontiguousarray(result_map, dtype=np.uint16)
+    if t.ndim != 2 or r.shape != t.shape:
+        raise AnnonetHipError(1, "score: a truth and a result map [H,W] of one shape")
+    net = _net_for_blobs(net)
+    pp, pr, lab = _score_outputs(1, max(classes, 0), prefill)
+    check(net.L.anh_score(net.h, _ptr(t), _ptr(r), classes, t.shape[0], t.shape[1], _ptr(pp), _ptr(pr), _ptr(lab)))
+    return pp[0], pr[0], int(lab[0])
+
+
 def _regions_outputs(out, tables, wanted):
     """(results..., tables) followed by the optional lists that were asked for"""
     return tuple(out) + (tables,) + tuple(arrays for want, arrays in wanted if want)

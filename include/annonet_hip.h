@@ -308,6 +308,37 @@ int anh_infer_regions_scaled_batch(anh_runtime* h, const uint8_t* const* images_
                                    const double* gains, const double* detection_levels, const anh_tiling_params* tiling,
                                    uint16_t* const* results, uint16_t* const* scaled_labels, uint32_t* const* blobs, float* const* blended_out,
                                    anh_region** regions, size_t* n_regions);
+/* ---- scoring result maps against their ground truth: the two confusion matrices of the inference program (annonet_infer_main.cpp:482-491
+ * per pixel, :202-272 per region, two-way) on the device ----
+ * truth and result are u16 label maps of one size, `classes` = K.  A pixel is LABELLED where truth < K (ANH_LABEL_IGNORE is not); a
+ * prediction >= K (65535: an all-NaN pixel) casts no vote.
+ *   labelled        the number of labelled pixels
+ *   per_pixel[t][p] the number of labelled pixels with truth == t and result == p < K
+ *   per_region      for each map M of (truth, result): M's regions are its blobs (anh_label_blobs_device: 8-connected, equal non-zero
+ *                   value, 65535 a value like any other) plus region 0 = all pixels where M == 0.  With T[c] / P[c] the number of the
+ *                   region's labelled pixels whose truth / result (< K) is c: no vote where T is all zero; t = first index of max(T);
+ *                   where t != 0 and P is not "background only" (P[0] > 0, nothing else) P[0] counts as 0; no vote where P is all zero;
+ *                   else per_region[t][first index of max(P)] += 1.  Ties go to the smaller class.
+ * One batched labelling of the 2n maps, one tally pass over the pixels, one launch over the regions: the number of launches does not
+ * depend on n, all sums are integer atomics (the same bits on every run), and image i of a batch equals the single call on that pair
+ * bit for bit.  The calls run on the handle's stream (replica 0 of a handle with several) and wait on the host twice whatever n is: for
+ * the blob counts, which size the vote table, and for the matrices.  Everything but the vote table is reserved before the first
+ * kernel; the table once the counts are known, and if that fails the call returns ANH_ERR_OOM and the handle stays usable.
+ * ANH_ERR_INVALID before anything is enqueued: classes outside 1..65535, n < 1, empty maps, height * width >= 2^31, 2n maps beyond the
+ * batched labeller's limit (2 * n * height * width, sides rounded up to 32, < 2^32 pixels), a NULL map.  `classes` need not be the net's.
+ * Counts of n >= 1 pairs of maps of ONE size; all outputs are OVERWRITTEN and are per image: per_pixel, per_region [n][classes][classes]
+ * u64, first index ground truth; labelled [n] u64 (any output may be NULL).  d_truth, d_result: [n][height][width], resident. */
+int anh_score_batch_device(anh_runtime* h, const uint16_t* d_truth, const uint16_t* d_result, int n, int classes, int height, int width,
+                           uint64_t* per_pixel, uint64_t* per_region, uint64_t* labelled);
+/* n = 1 */
+int anh_score_device(anh_runtime* h, const uint16_t* d_truth, const uint16_t* d_result, int classes, int height, int width,
+                     uint64_t* per_pixel, uint64_t* per_region, uint64_t* labelled);
+/* host maps (n pointers each), uploaded at 2 bytes per pixel and map */
+int anh_score_batch(anh_runtime* h, const uint16_t* const* truth, const uint16_t* const* result, int n, int classes, int height, int width,
+                    uint64_t* per_pixel, uint64_t* per_region, uint64_t* labelled);
+/* n = 1, host maps */
+int anh_score(anh_runtime* h, const uint16_t* truth, const uint16_t* result, int classes, int height, int width,
+              uint64_t* per_pixel, uint64_t* per_region, uint64_t* labelled);
 /* label rows [row0, row1) of device-resident blended planes (find_label, annonet_infer.cpp:170-185): the second half of a
    sharded annonet_infer(), run after the ranks have exchanged the plane sums of their overlapping tiles */
 int anh_argmax_device(anh_runtime* h, const float* d_blended, int height, int width, int row0, int row1, const double* gains, uint16_t* d_result);

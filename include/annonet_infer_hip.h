@@ -303,4 +303,41 @@ inline void annonet_infer_regions_scaled_batch(NetPimpl::RuntimeNet& net, const 
     if (temp.keep_blended_output) d::store_planes(temp, planes, K, sh, sw);
 }
 
+// What the reference's inference program does with a result after annonet_infer() (annonet_infer_main.cpp:482-491, :202-272), on the GPU
+// (anh_score_batch): per image the labelled pixels, the per-pixel counts and the two-way per-region votes, [classes][classes] each with the
+// ground truth as the first index.  The rule is written out in annonet_hip.h.  The maps of one call have ONE size; truth_maps[i] belongs
+// to result_maps[i]; a truth value >= classes (65535 = ignore) is unlabelled, a result value >= classes casts no vote.
+struct annonet_score_counts {
+    std::vector<uint64_t> labelled;      // [n]
+    std::vector<uint64_t> per_pixel;     // [n][classes][classes]
+    std::vector<uint64_t> per_region;    // [n][classes][classes]
+};
+
+inline void annonet_score(NetPimpl::RuntimeNet& net, const std::vector<const dlib::matrix<uint16_t>*>& truth_maps,
+                          const std::vector<const dlib::matrix<uint16_t>*>& result_maps, int classes, annonet_score_counts& counts) {
+    if (truth_maps.empty() || truth_maps.size() != result_maps.size()) throw std::runtime_error("annonet_score: one result map per truth map, at least one pair");
+    if (classes < 1) throw std::runtime_error("annonet_score: the class count must be at least 1");
+    const int n = (int)truth_maps.size(), H = (int)truth_maps[0]->nr(), W = (int)truth_maps[0]->nc();
+    std::vector<const uint16_t*> truth((size_t)n), result((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if ((int)truth_maps[i]->nr() != H || (int)truth_maps[i]->nc() != W || (int)result_maps[i]->nr() != H || (int)result_maps[i]->nc() != W)
+            throw std::runtime_error("annonet_score: the maps of a call must have one size");
+        if (H < 1 || W < 1) throw std::runtime_error("annonet_score: empty maps");
+        truth[i] = &*truth_maps[i]->begin();
+        result[i] = &*result_maps[i]->begin();
+    }
+    const size_t cells = (size_t)n * classes * classes;
+    counts.labelled.assign((size_t)n, 0);
+    counts.per_pixel.assign(cells, 0);
+    counts.per_region.assign(cells, 0);
+    NetPimpl::check(anh_score_batch(net.handle(), truth.data(), result.data(), n, classes, H, W, counts.per_pixel.data(), counts.per_region.data(),
+                                    counts.labelled.data()));
+}
+
+// one pair of maps
+inline void annonet_score(NetPimpl::RuntimeNet& net, const dlib::matrix<uint16_t>& truth_map, const dlib::matrix<uint16_t>& result_map, int classes,
+                          annonet_score_counts& counts) {
+    annonet_score(net, std::vector<const dlib::matrix<uint16_t>*>{&truth_map}, std::vector<const dlib::matrix<uint16_t>*>{&result_map}, classes, counts);
+}
+
 #endif  // ANNONET_INFER_HIP_H
