@@ -759,7 +759,7 @@ void run_share(Engine& e, const HostInfer& c, int lo, int hi) {
     reserve_stage(e, (size_t)m, plane, planes);
     if (c.resized()) { e.stage_original.reserve((size_t)m * full * C); e.stage_upsampled.reserve((size_t)m * full * 2); }
     if (c.tail == Tail::filter) e.stage_out.reserve(detection_scratch_bytes(plane, K));
-    if (c.tail == Tail::regions) { if (c.batch) (void)e.reserve_blobs_batch(m, c.h, c.w, K, true); else (void)e.reserve_blobs(c.h, c.w, K, true); }
+    if (c.tail == Tail::regions) (void)e.reserve_blobs(m, c.h, c.w, K, true);
     if (c.batch) e.reserve_infer_batch(m, c.h, c.w, c.tiles, planes);   // the forward's own, ahead of the shrink
     uint8_t* d_image = e.stage_image.as<uint8_t>();
     float* d_planes = planes ? e.stage_blended.as<float>() : nullptr;
@@ -775,10 +775,9 @@ void run_share(Engine& e, const HostInfer& c, int lo, int hi) {
     const uint32_t* d_blobs = nullptr;
     if (c.tail == Tail::filter)
         for (int i = 0; i < m; ++i) (void)apply_detection_levels(e, c.levels, K, c.h, c.w, d_planes + (size_t)i * K * plane, d_labels + (size_t)i * plane);
-    if (c.tail == Tail::regions) {   // ONE call for the share's m maps: a single-image form keeps Engine::regions' launches
+    if (c.tail == Tail::regions) {   // ONE call for the share's m maps
         anh_region* t = nullptr;
-        if (c.batch) d_blobs = e.regions_batch(d_labels, d_planes, m, K, c.h, c.w, c.levels, /*filter=*/true, nullptr, &t, c.n_regions + lo);
-        else d_blobs = e.regions(d_labels, d_planes, K, c.h, c.w, c.levels, /*filter=*/true, nullptr, &t, c.n_regions + lo);
+        d_blobs = e.regions(d_labels, d_planes, m, K, c.h, c.w, c.levels, /*filter=*/true, nullptr, &t, c.n_regions + lo, /*stacked=*/c.batch);
         table.reset(t);
     }
     if (c.resized()) {
@@ -867,20 +866,44 @@ int anh_infer(anh_runtime* h, const uint8_t* image, int height, int width, const
     });
 }
 
-// ---- connected blobs and the region table (Engine::label_blobs / regions) ----
+// ---- connected blobs and the region table (Engine::label_blobs / regions): a single-image entry point is the batch one with n = 1, behind
+// its own size check ----
 namespace {
 void require_blob_map_size(int height, int width) {
     ANH_REQUIRE(height >= 1 && width >= 1, "empty label map");
     ANH_REQUIRE((int64_t)height * width < ((int64_t)1 << 31), "blob labelling is limited to height * width < 2^31 pixels");
 }
+void require_blob_batch_size(int n, int height, int width) {
+    ANH_REQUIRE(n >= 1, "the batch needs at least one image");
+    require_blob_map_size(height, width);
+    ANH_REQUIRE(blob_batch_fits(n, height, width), "blob labelling of a batch is limited to n * height * width (sides rounded up to 32) < 2^32 pixels");
+}
+// what the entry points of either form do after their size check (first: a size beyond the limit is refused whatever else is wrong)
+void label_blobs_device(anh_runtime* h, const uint16_t* d_labels, int n, bool batch, int height, int width, uint32_t* d_blobs, uint32_t* counts) {
+    ANH_REQUIRE(h && d_labels && d_blobs && counts, "null argument");
+    DeviceScope scope(h->reps.device_of(0));
+    h->reps.engine(0).label_blobs(d_labels, n, height, width, d_blobs, counts, batch);
+}
+void regions_device(anh_runtime* h, uint16_t* d_labels, const float* d_blended, int n, bool batch, int classes, int height, int width, const double* detection_levels,
+                    int apply_filter, uint32_t* d_blobs, anh_region** regions, size_t* n_regions) {
+    ANH_REQUIRE(classes >= 1 && classes <= 65535, "regions: the class count must be within 1..65535");
+    if (detection_levels) for (int k = 0; k < classes; ++k) ANH_REQUIRE(detection_levels[k] >= 0.0, "detection levels must be >= 0");
+    ANH_REQUIRE(h && d_labels && d_blended && regions && n_regions, "null argument");
+    DeviceScope scope(h->reps.device_of(0));
+    (void)h->reps.engine(0).regions(d_labels, d_blended, n, classes, height, width, detection_levels, apply_filter != 0, d_blobs, regions, n_regions, batch);
+}
+// what the four host-buffer forms share: the regions tail on a checked HostInfer
+void run_regions(anh_runtime* h, HostInfer c, uint32_t* const* blobs, anh_region** regions, size_t* n_regions) {
+    c.tail = HostInfer::Tail::regions;
+    c.blobs = blobs; c.regions = regions; c.n_regions = n_regions;
+    run_host_infer(h, c);
+}
 }  // namespace
 
 int anh_label_blobs_device(anh_runtime* h, const uint16_t* d_labels, int height, int width, uint32_t* d_blobs, uint32_t* count) {
     return guarded([&] {
-        require_blob_map_size(height, width);   // first: a size beyond the limit is refused whatever else is wrong
-        ANH_REQUIRE(h && d_labels && d_blobs && count, "null argument");
-        DeviceScope scope(h->reps.device_of(0));
-        *count = h->reps.engine(0).label_blobs(d_labels, height, width, d_blobs);
+        require_blob_map_size(height, width);
+        label_blobs_device(h, d_labels, 1, false, height, width, d_blobs, count);
     });
 }
 
@@ -888,10 +911,7 @@ int anh_regions_device(anh_runtime* h, uint16_t* d_labels, const float* d_blende
                        int apply_filter, uint32_t* d_blobs, anh_region** regions, size_t* n_regions) {
     return guarded([&] {
         require_blob_map_size(height, width);
-        ANH_REQUIRE(classes >= 1 && classes <= 65535, "regions: the class count must be within 1..65535");
-        ANH_REQUIRE(h && d_labels && d_blended && regions && n_regions, "null argument");
-        DeviceScope scope(h->reps.device_of(0));
-        (void)h->reps.engine(0).regions(d_labels, d_blended, classes, height, width, detection_levels, apply_filter != 0, d_blobs, regions, n_regions);
+        regions_device(h, d_labels, d_blended, 1, false, classes, height, width, detection_levels, apply_filter, d_blobs, regions, n_regions);
     });
 }
 
@@ -918,37 +938,16 @@ int anh_infer_regions(anh_runtime* h, const uint8_t* image, int height, int widt
     return guarded([&] {
         require_blob_map_size(height, width);
         ANH_REQUIRE(h && image && result && regions && n_regions, "null argument");
-        HostInfer c(h, &image, 1, false, height, width, 1.0, height, width, gains, detection_levels, tiling, &result, nullptr, &blended_out);
-        c.tail = HostInfer::Tail::regions;   // the blobs are those of the WHOLE label map: replica 0 alone, as anh_infer's filter
-        c.blobs = &blobs; c.regions = regions; c.n_regions = n_regions;
-        run_host_infer(h, c);
+        // the blobs are those of the WHOLE label map: replica 0 alone, as anh_infer's filter
+        run_regions(h, HostInfer(h, &image, 1, false, height, width, 1.0, height, width, gains, detection_levels, tiling, &result, nullptr, &blended_out), &blobs, regions,
+                    n_regions);
     });
 }
 
-// ---- the same over n maps of one size (Engine::label_blobs_batch / regions_batch) ----
-namespace {
-void require_blob_batch_size(int n, int height, int width) {
-    ANH_REQUIRE(n >= 1, "the batch needs at least one image");
-    require_blob_map_size(height, width);
-    ANH_REQUIRE(blob_batch_fits(n, height, width), "blob labelling of a batch is limited to n * height * width (sides rounded up to 32) < 2^32 pixels");
-}
-void require_levels(const double* detection_levels, int classes) {
-    if (detection_levels) for (int k = 0; k < classes; ++k) ANH_REQUIRE(detection_levels[k] >= 0.0, "detection levels must be >= 0");
-}
-// what the three host-buffer forms share: the regions tail on a checked HostInfer
-void run_regions(anh_runtime* h, HostInfer c, uint32_t* const* blobs, anh_region** regions, size_t* n_regions) {
-    c.tail = HostInfer::Tail::regions;
-    c.blobs = blobs; c.regions = regions; c.n_regions = n_regions;
-    run_host_infer(h, c);
-}
-}  // namespace
-
 int anh_label_blobs_batch_device(anh_runtime* h, const uint16_t* d_labels, int n, int height, int width, uint32_t* d_blobs, uint32_t* counts) {
     return guarded([&] {
-        require_blob_batch_size(n, height, width);   // first: a size beyond the limit is refused whatever else is wrong
-        ANH_REQUIRE(h && d_labels && d_blobs && counts, "null argument");
-        DeviceScope scope(h->reps.device_of(0));
-        h->reps.engine(0).label_blobs_batch(d_labels, n, height, width, d_blobs, counts);
+        require_blob_batch_size(n, height, width);
+        label_blobs_device(h, d_labels, n, true, height, width, d_blobs, counts);
     });
 }
 
@@ -956,11 +955,7 @@ int anh_regions_batch_device(anh_runtime* h, uint16_t* d_labels, const float* d_
                              int apply_filter, uint32_t* d_blobs, anh_region** regions, size_t* n_regions) {
     return guarded([&] {
         require_blob_batch_size(n, height, width);
-        ANH_REQUIRE(classes >= 1 && classes <= 65535, "regions: the class count must be within 1..65535");
-        require_levels(detection_levels, classes);
-        ANH_REQUIRE(h && d_labels && d_blended && regions && n_regions, "null argument");
-        DeviceScope scope(h->reps.device_of(0));
-        (void)h->reps.engine(0).regions_batch(d_labels, d_blended, n, classes, height, width, detection_levels, apply_filter != 0, d_blobs, regions, n_regions);
+        regions_device(h, d_labels, d_blended, n, true, classes, height, width, detection_levels, apply_filter, d_blobs, regions, n_regions);
     });
 }
 

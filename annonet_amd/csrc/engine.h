@@ -178,27 +178,22 @@ class Engine {
     std::vector<float> host_out;
 
     // ---- connected blobs and the region table (kernels_blobs.hip; annonet_infer.cpp:194-223) ----
-    // scratch of one map of H x W with K detection levels: [parent | block sums | count | levels | seed flags]; own_map: a blob map of the
-    // engine's own as well (the caller gives none).  Nothing is enqueued.
-    struct BlobScratch { int* parent; unsigned* sums; unsigned* count; double* det; uint8_t* flags; };
-    BlobScratch reserve_blobs(int H, int W, int K, bool own_map);
+    // Everything works on n maps of one size lying back to back ([n][H][W], planes [n][K][H][W]) with launches that do not depend on n;
+    // one map is a stack with n = 1.  `stacked` only names the profiler tags after the form the caller asked for: label_blobs /
+    // blob_regions for a single-image entry point, label_blobs_batch / blob_regions_batch for a batch one.
+    // Scratch of n maps with K detection levels: [parents | block sums | counts | row offsets | levels | seed flags]; own_map: blob maps of
+    // the engine's own as well (the caller gives none).  Nothing is enqueued.
+    struct BlobScratch { int* parent; unsigned* sums; unsigned* counts; unsigned long long* offsets; double* det; uint8_t* flags; };
+    BlobScratch reserve_blobs(int n, int H, int W, int K, bool own_map);
     DevBuf blob_scratch, blob_map, blob_table;
-    // d_blobs [H][W] = the blob numbers of d_labels; returns blobs + 1.  Synchronises (the count comes back).
-    uint32_t label_blobs(const uint16_t* d_labels, int H, int W, uint32_t* d_blobs);
-    // the table of d_labels' blobs as a malloc'd block of *n rows (the caller owns it); levels_host: K doubles or null; filter: relabel the
-    // blobs without a seed to 0 when a level is positive.  d_blobs may be null.  Returns the blob map it used.  Synchronises twice.
-    uint32_t* regions(uint16_t* d_labels, const float* d_blended, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
-                      anh_region** out, size_t* n);
-    // The same over n maps of one size lying back to back ([n][H][W], planes [n][K][H][W]), with launches that do not depend on n
-    // (kernels_blobs.hip, the `_batch_` kernels).  Scratch: [parents | block sums | counts | row offsets | levels | seed flags].
-    struct BlobBatchScratch { int* parent; unsigned* sums; unsigned* counts; unsigned long long* offsets; double* det; uint8_t* flags; };
-    BlobBatchScratch reserve_blobs_batch(int n, int H, int W, int K, bool own_map);
-    // counts: n host values, blobs + 1 each.  Synchronises once.
-    void label_blobs_batch(const uint16_t* d_labels, int n, int H, int W, uint32_t* d_blobs, uint32_t* counts);
-    // *out: ONE malloc'd block with image 0's rows, then image 1's, ...; n_regions: n host values; blob numbers restart at 1 per image.
-    // Synchronises twice whatever n is: for the counts (the host sums them into the row offsets) and for the table.
-    uint32_t* regions_batch(uint16_t* d_labels, const float* d_blended, int n, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
-                            anh_region** out, size_t* n_regions);
+    // d_blobs [n][H][W] = the blob numbers of d_labels, restarting at 1 per image; counts: n host values, blobs + 1 each.  Synchronises once.
+    void label_blobs(const uint16_t* d_labels, int n, int H, int W, uint32_t* d_blobs, uint32_t* counts, bool stacked);
+    // the table of d_labels' blobs as ONE malloc'd block (the caller owns it) with image 0's rows, then image 1's, ...; n_regions: n host
+    // values; levels_host: K doubles or null; filter: relabel the blobs without a seed to 0 when a level is positive.  d_blobs may be null.
+    // Returns the blob maps it used.  Synchronises twice whatever n is: for the counts (the host sums them into the row offsets) and for
+    // the table.
+    uint32_t* regions(uint16_t* d_labels, const float* d_blended, int n, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
+                      anh_region** out, size_t* n_regions, bool stacked);
 
     // ---- scoring result maps against their ground truth (kernels_score.hip; annonet_infer_main.cpp:482-491, RegionScorer) ----
     // Everything a score call of n pairs of H x W maps with K classes needs but the vote table, reserved before anything is enqueued.
@@ -206,7 +201,7 @@ class Engine {
     uint16_t* reserve_score(int n, int K, int H, int W);
     DevBuf score_maps, score_votes, score_out;
     std::vector<uint64_t> host_score;   // score_out as it comes back
-    // the counts of the stack reserve_score returned: per_pixel, per_region [n][K][K], labelled [n], host u64, each may be null.  ONE batched
+    // the counts of the stack reserve_score returned: per_pixel, per_region [n][K][K], labelled [n], host u64, each may be null.  ONE
     // labelling of the 2n maps, the tally, the decide launch.  Synchronises twice whatever n is: for the counts (they size the vote
     // table) and for the matrices.
     void score_stacked(int n, int K, int H, int W, uint64_t* per_pixel, uint64_t* per_region, uint64_t* labelled);

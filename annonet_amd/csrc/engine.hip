@@ -1231,79 +1231,12 @@ void Engine::resize_labels_batch(const uint16_t* d_src, int count, int src_h, in
     prof.end(stream, tok);
 }
 
-// ---- connected blobs and the region table ----
-Engine::BlobScratch Engine::reserve_blobs(int H, int W, int K, bool own_map) {
-    ANH_REQUIRE(H >= 1 && W >= 1, "empty label map");
-    ANH_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), "blob labelling is limited to height * width < 2^31 pixels");
-    const size_t plane = (size_t)H * W;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t sums_off = up(plane * 4), count_off = sums_off + up(blob_scan_blocks((int64_t)plane) * 4), det_off = count_off + 256;
-    const size_t flags_off = det_off + up((size_t)std::max(K, 1) * sizeof(double));
-    blob_scratch.reserve(flags_off + plane);
-    if (own_map) blob_map.reserve(plane * 4);
-    char* base = blob_scratch.as<char>();
-    return BlobScratch{reinterpret_cast<int*>(base), reinterpret_cast<unsigned*>(base + sums_off), reinterpret_cast<unsigned*>(base + count_off),
-                       reinterpret_cast<double*>(base + det_off), reinterpret_cast<uint8_t*>(base + flags_off)};
-}
-
-uint32_t Engine::label_blobs(const uint16_t* d_labels, int H, int W, uint32_t* d_blobs) {
-    const BlobScratch b = reserve_blobs(H, W, 0, false);
-    const double px = (double)H * W;
-    const int tok = prof.begin(stream, "label_blobs", 0, px * 40.0);
-    launch_blob_label(d_labels, H, W, b.parent, d_blobs, b.sums, b.count, stream);
-    launch_blob_number(b.parent, d_blobs, d_labels, H, W, nullptr, stream);
-    prof.end(stream, tok);
-    uint32_t count = 0;
-    HIP_CHECK(hipMemcpyAsync(&count, b.count, sizeof count, hipMemcpyDeviceToHost, stream));
-    wait_stream(stream, bounded_waits);
-    return count;
-}
-
-uint32_t* Engine::regions(uint16_t* d_labels, const float* d_blended, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
-                          anh_region** out, size_t* n) {
-    ANH_REQUIRE(K >= 1 && K <= 65535, "regions: the class count must be within 1..65535");
-    const BlobScratch b = reserve_blobs(H, W, K, d_blobs == nullptr);   // everything but the table, before the first kernel
-    if (!d_blobs) d_blobs = blob_map.as<uint32_t>();
-    bool positive = false;
-    std::vector<double> levels((size_t)K, 0.0);   // no positive level: zeros (read by the upload below, which the first wait covers)
-    if (levels_host) for (int k = 0; k < K; ++k) { ANH_REQUIRE(levels_host[k] >= 0.0, "detection levels must be >= 0"); positive = positive || levels_host[k] > 0.0; }
-    if (positive) levels.assign(levels_host, levels_host + K);
-    const double px = (double)H * W;
-    int tok = prof.begin(stream, "label_blobs", 0, px * 40.0 + px * 11.0);
-    HIP_CHECK(hipMemcpyAsync(b.det, levels.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice, stream));
-    launch_detection_seeds(d_blended, d_labels, K, H, W, b.det, b.flags, stream);
-    launch_blob_label(d_labels, H, W, b.parent, d_blobs, b.sums, b.count, stream);
-    prof.end(stream, tok);
-    uint32_t count = 0;
-    HIP_CHECK(hipMemcpyAsync(&count, b.count, sizeof count, hipMemcpyDeviceToHost, stream));
-    wait_stream(stream, bounded_waits);
-    ANH_REQUIRE(count >= 1, "blob labelling returned no count");
-    const uint32_t rows = count - 1;
-    // the one reservation whose size is known only now; a failure leaves the handle as it was (the blob map stays un-numbered)
-    if (rows) blob_table.reserve((size_t)rows * sizeof(anh_region));
-    anh_region* host = static_cast<anh_region*>(std::malloc(std::max<size_t>(1, (size_t)rows * sizeof(anh_region))));
-    if (!host) fail(ANH_ERR_OOM, "host allocation of the region table failed");
-    try {
-        anh_region* table = rows ? blob_table.as<anh_region>() : nullptr;
-        tok = prof.begin(stream, "blob_regions", 0, px * 19.0);
-        launch_blob_number(b.parent, d_blobs, d_labels, H, W, table, stream);
-        launch_blob_stats(d_blobs, d_labels, d_blended, K, H, W, b.flags, table, rows, positive, stream);
-        if (filter && positive && rows) launch_blob_filter(d_labels, d_blobs, table, (int64_t)H * W, stream);
-        prof.end(stream, tok);
-        if (rows) HIP_CHECK(hipMemcpyAsync(host, table, (size_t)rows * sizeof(anh_region), hipMemcpyDeviceToHost, stream));
-        wait_stream(stream, bounded_waits);
-    } catch (...) { std::free(host); throw; }
-    *out = host;
-    *n = rows;
-    return d_blobs;
-}
-
-// ---- ... of n maps of one size lying back to back ----
-Engine::BlobBatchScratch Engine::reserve_blobs_batch(int n, int H, int W, int K, bool own_map) {
+// ---- connected blobs and the region table: n maps of one size lying back to back, one map being a stack with n = 1 ----
+Engine::BlobScratch Engine::reserve_blobs(int n, int H, int W, int K, bool own_map) {
     ANH_REQUIRE(n >= 1, "the stack needs at least one label map");
     ANH_REQUIRE(H >= 1 && W >= 1, "empty label map");
     ANH_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), "blob labelling is limited to height * width < 2^31 pixels");
-    ANH_REQUIRE(blob_batch_fits(n, H, W), "blob labelling of a stack is limited to n * height * width (sides rounded up to 32) < 2^32 pixels");
+    ANH_REQUIRE(blob_stack_fits(n, H, W), "blob labelling of a stack is limited to n * height * width (sides rounded up to 32) < 2^32 pixels");
     const size_t plane = (size_t)H * W, all = (size_t)n * plane;
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t sums_off = up(all * 4), counts_off = sums_off + up((size_t)n * blob_scan_blocks((int64_t)plane) * 4), offsets_off = counts_off + up((size_t)n * 4);
@@ -1311,60 +1244,67 @@ Engine::BlobBatchScratch Engine::reserve_blobs_batch(int n, int H, int W, int K,
     blob_scratch.reserve(flags_off + all);
     if (own_map) blob_map.reserve(all * 4);
     char* base = blob_scratch.as<char>();
-    return BlobBatchScratch{reinterpret_cast<int*>(base), reinterpret_cast<unsigned*>(base + sums_off), reinterpret_cast<unsigned*>(base + counts_off),
-                            reinterpret_cast<unsigned long long*>(base + offsets_off), reinterpret_cast<double*>(base + det_off),
-                            reinterpret_cast<uint8_t*>(base + flags_off)};
+    return BlobScratch{reinterpret_cast<int*>(base), reinterpret_cast<unsigned*>(base + sums_off), reinterpret_cast<unsigned*>(base + counts_off),
+                       reinterpret_cast<unsigned long long*>(base + offsets_off), reinterpret_cast<double*>(base + det_off),
+                       reinterpret_cast<uint8_t*>(base + flags_off)};
 }
 
-void Engine::label_blobs_batch(const uint16_t* d_labels, int n, int H, int W, uint32_t* d_blobs, uint32_t* counts) {
-    const BlobBatchScratch b = reserve_blobs_batch(n, H, W, 0, false);
+void Engine::label_blobs(const uint16_t* d_labels, int n, int H, int W, uint32_t* d_blobs, uint32_t* counts, bool stacked) {
+    const BlobScratch b = reserve_blobs(n, H, W, 0, false);
     const double px = (double)n * H * W;
-    const int tok = prof.begin(stream, "label_blobs_batch", 0, px * 40.0);
-    launch_blob_label_batch(d_labels, n, H, W, b.parent, d_blobs, b.sums, b.counts, stream);
-    launch_blob_number_batch(b.parent, d_blobs, d_labels, n, H, W, nullptr, nullptr, stream);
+    const int tok = prof.begin(stream, stacked ? "label_blobs_batch" : "label_blobs", 0, px * 40.0);
+    launch_blob_label(d_labels, n, H, W, b.parent, d_blobs, b.sums, b.counts, stream);
+    launch_blob_number(b.parent, d_blobs, d_labels, n, H, W, nullptr, nullptr, stream);
     prof.end(stream, tok);
     HIP_CHECK(hipMemcpyAsync(counts, b.counts, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     wait_stream(stream, bounded_waits);
 }
 
-uint32_t* Engine::regions_batch(uint16_t* d_labels, const float* d_blended, int n, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
-                                anh_region** out, size_t* n_regions) {
+// offsets[i] = the rows of the maps before map i, a map holding counts[i] - less rows (the labeller's count is blobs + 1: less = 1 for a
+// table of blobs, 0 for one of regions, region 0 included); returns their total, which has to fit the 32-bit row numbers
+static uint32_t rows_before(const std::vector<uint32_t>& counts, uint32_t less, const char* table, std::vector<unsigned long long>& offsets) {
+    offsets.assign(counts.size(), 0);
+    unsigned long long total = 0;
+    for (size_t i = 0; i < counts.size(); ++i) {
+        ANH_REQUIRE(counts[i] >= 1, "blob labelling returned no count");
+        offsets[i] = total;
+        total += counts[i] - less;
+    }
+    if (total > 0xFFFFFFFFull) fail(ANH_ERR_OOM, std::string("the ") + table + " table of the stack would hold more than 2^32 rows");
+    return (uint32_t)total;
+}
+
+uint32_t* Engine::regions(uint16_t* d_labels, const float* d_blended, int n, int K, int H, int W, const double* levels_host, bool filter, uint32_t* d_blobs,
+                          anh_region** out, size_t* n_regions, bool stacked) {
     ANH_REQUIRE(K >= 1 && K <= 65535, "regions: the class count must be within 1..65535");
-    const BlobBatchScratch b = reserve_blobs_batch(n, H, W, K, d_blobs == nullptr);   // everything but the table, before the first kernel
+    const BlobScratch b = reserve_blobs(n, H, W, K, d_blobs == nullptr);   // everything but the table, before the first kernel
     if (!d_blobs) d_blobs = blob_map.as<uint32_t>();
     bool positive = false;
-    std::vector<double> levels((size_t)K, 0.0);
+    std::vector<double> levels((size_t)K, 0.0);   // no positive level: zeros (read by the upload below, which the first wait covers)
     if (levels_host) for (int k = 0; k < K; ++k) { ANH_REQUIRE(levels_host[k] >= 0.0, "detection levels must be >= 0"); positive = positive || levels_host[k] > 0.0; }
     if (positive) levels.assign(levels_host, levels_host + K);
     const double px = (double)n * H * W;
-    int tok = prof.begin(stream, "label_blobs_batch", 0, px * 40.0 + px * 11.0);
+    int tok = prof.begin(stream, stacked ? "label_blobs_batch" : "label_blobs", 0, px * 40.0 + px * 11.0);
     HIP_CHECK(hipMemcpyAsync(b.det, levels.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice, stream));
-    launch_detection_seeds_batch(d_blended, d_labels, K, n, H, W, b.det, b.flags, stream);
-    launch_blob_label_batch(d_labels, n, H, W, b.parent, d_blobs, b.sums, b.counts, stream);
+    launch_detection_seeds(d_blended, d_labels, K, n, H, W, b.det, b.flags, stream);
+    launch_blob_label(d_labels, n, H, W, b.parent, d_blobs, b.sums, b.counts, stream);
     prof.end(stream, tok);
     std::vector<uint32_t> counts((size_t)n, 0);
     HIP_CHECK(hipMemcpyAsync(counts.data(), b.counts, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     wait_stream(stream, bounded_waits);   // the first of the call's two waits: the counts size the table
-    std::vector<unsigned long long> offsets((size_t)n, 0);   // (read by the upload below, which the second wait covers)
-    unsigned long long total = 0;
-    for (int i = 0; i < n; ++i) {
-        ANH_REQUIRE(counts[(size_t)i] >= 1, "blob labelling returned no count");
-        offsets[(size_t)i] = total;
-        total += counts[(size_t)i] - 1;
-    }
-    if (total > 0xFFFFFFFFull) fail(ANH_ERR_OOM, "the region table of the stack would hold more than 2^32 rows");
-    const uint32_t rows = (uint32_t)total;
+    std::vector<unsigned long long> offsets;   // (read by the upload below, which the second wait covers)
+    const uint32_t rows = rows_before(counts, 1, "region", offsets);
     // the one reservation whose size is known only now; a failure leaves the handle as it was (the blob maps stay un-numbered)
     if (rows) blob_table.reserve((size_t)rows * sizeof(anh_region));
     anh_region* host = static_cast<anh_region*>(std::malloc(std::max<size_t>(1, (size_t)rows * sizeof(anh_region))));
     if (!host) fail(ANH_ERR_OOM, "host allocation of the region table failed");
     try {
         anh_region* table = rows ? blob_table.as<anh_region>() : nullptr;
-        tok = prof.begin(stream, "blob_regions_batch", 0, px * 19.0);
+        tok = prof.begin(stream, stacked ? "blob_regions_batch" : "blob_regions", 0, px * 19.0);
         HIP_CHECK(hipMemcpyAsync(b.offsets, offsets.data(), (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-        launch_blob_number_batch(b.parent, d_blobs, d_labels, n, H, W, table, b.offsets, stream);
-        launch_blob_stats_batch(d_blobs, d_labels, d_blended, K, n, H, W, b.flags, table, b.offsets, rows, positive, stream);
-        if (filter && positive && rows) launch_blob_filter_batch(d_labels, d_blobs, table, b.offsets, n, (int64_t)H * W, stream);
+        launch_blob_number(b.parent, d_blobs, d_labels, n, H, W, table, b.offsets, stream);
+        launch_blob_stats(d_blobs, d_labels, d_blended, K, n, H, W, b.flags, table, b.offsets, rows, positive, stream);
+        if (filter && positive && rows) launch_blob_filter(d_labels, d_blobs, table, b.offsets, n, (int64_t)H * W, stream);
         prof.end(stream, tok);
         if (rows) HIP_CHECK(hipMemcpyAsync(host, table, (size_t)rows * sizeof(anh_region), hipMemcpyDeviceToHost, stream));
         wait_stream(stream, bounded_waits);   // the second wait: the table
@@ -1378,7 +1318,7 @@ uint32_t* Engine::regions_batch(uint16_t* d_labels, const float* d_blended, int 
 uint16_t* Engine::reserve_score(int n, int K, int H, int W) {
     ANH_REQUIRE(n >= 1, "score: the batch needs at least one pair of maps");
     ANH_REQUIRE(K >= 1 && K <= 65535, "score: the class count must be within 1..65535");
-    (void)reserve_blobs_batch(2 * n, H, W, 0, true);   // the labeller's scratch and the 2n blob maps (checks the sizes)
+    (void)reserve_blobs(2 * n, H, W, 0, true);   // the labeller's scratch and the 2n blob maps (checks the sizes)
     const size_t plane = (size_t)H * W, cells = (size_t)n * K * K;
     score_maps.reserve(2 * (size_t)n * plane * sizeof(uint16_t));
     score_out.reserve(((size_t)n + 2 * cells) * sizeof(uint64_t));   // [labelled | per pixel | per region]
@@ -1390,20 +1330,13 @@ void Engine::score_stacked(int n, int K, int H, int W, uint64_t* per_pixel, uint
     const uint16_t* maps = reserve_score(n, K, H, W);   // (the caller reserved already: nothing moves)
     uint32_t* blobs = blob_map.as<uint32_t>();
     std::vector<uint32_t> counts((size_t)(2 * n), 0);
-    label_blobs_batch(maps, 2 * n, H, W, blobs, counts.data());   // the first of the call's two waits
-    std::vector<unsigned long long> offsets((size_t)(2 * n), 0);   // (read by the upload below, which the second wait covers)
-    unsigned long long total = 0;
-    for (int i = 0; i < 2 * n; ++i) {
-        ANH_REQUIRE(counts[(size_t)i] >= 1, "blob labelling returned no count");
-        offsets[(size_t)i] = total;
-        total += counts[(size_t)i];   // blobs + 1: the map's regions, region 0 included
-    }
-    if (total > 0xFFFFFFFFull) fail(ANH_ERR_OOM, "the vote table of the stack would hold more than 2^32 rows");
-    const uint32_t rows = (uint32_t)total;
+    label_blobs(maps, 2 * n, H, W, blobs, counts.data(), /*stacked=*/true);   // the first of the call's two waits
+    std::vector<unsigned long long> offsets;   // (read by the upload below, which the second wait covers)
+    const uint32_t rows = rows_before(counts, 0, "vote", offsets);   // blobs + 1: the map's regions, region 0 included
     // the one reservation whose size is known only now; a failure leaves the handle as it was
     const size_t vote_bytes = (size_t)rows * ((size_t)K + 1) * sizeof(unsigned);
     score_votes.reserve(vote_bytes);
-    const BlobBatchScratch b = reserve_blobs_batch(2 * n, H, W, 0, true);
+    const BlobScratch b = reserve_blobs(2 * n, H, W, 0, true);
     const size_t cells = (size_t)n * K * K, out_words = (size_t)n + 2 * cells;
     unsigned long long* out = score_out.as<unsigned long long>();
     const double px = (double)n * H * W;

@@ -306,41 +306,37 @@ void launch_crop_weights(const uint16_t* d_labels, const float* d_table, int n, 
 // read-back each; the last one is the quiet round that ends the loop)
 int run_detection_filter(const float* d_blended, uint16_t* d_labels, int k, int h, int w, const double* d_det, uint8_t* d_flags, int* d_changed,
                           hipStream_t s);
-// the filter's first launch on its own: flags[p] = 1 where pixel p is a detection seed (ANH_DET_SEED_REFERENCE_ORDER honoured); H*W bytes
-void launch_detection_seeds(const float* d_blended, const uint16_t* d_labels, int k, int h, int w, const double* d_det, uint8_t* d_flags, hipStream_t s);
-// connected blobs of a u16 label map [h][w] with h * w < 2^31 (kernels_blobs.hip): 8-connected sets of equal non-zero label, numbered
-// 1, 2, ... in raster order of their first pixel.  No launch waits for another workgroup of the same launch.
+// the filter's first launch on its own, over n images lying back to back by ONE launch: flags [n][h][w] from d_blended [n][k][h][w] and
+// d_labels [n][h][w]; flags[p] = 1 where pixel p is a detection seed (ANH_DET_SEED_REFERENCE_ORDER honoured, inside the image's own plane)
+void launch_detection_seeds(const float* d_blended, const uint16_t* d_labels, int k, int n, int h, int w, const double* d_det, uint8_t* d_flags, hipStream_t s);
+// connected blobs of n u16 label maps of one size lying back to back, [n][h][w] (kernels_blobs.hip): 8-connected sets of equal non-zero
+// label, numbered 1, 2, ... in raster order of their first pixel, the numbers restarting at 1 in every image.  One map is a stack with
+// n = 1.  The number of launches does not depend on n, and an image receives the same bits whatever stack it lies in.  No launch waits
+// for another workgroup of the same launch.
 constexpr int kBlobTile = 32;              // side of the tiles the local pass labels in LDS
-size_t blob_scan_blocks(int64_t pixels);   // words of d_sums
-// local, seam, flatten, scan, rank.  Afterwards *d_count = blobs + 1, d_blobs[p] = root(p) + 1 (0: background) and the root's slot of
-// d_parent holds the blob's number: launch_blob_number finishes d_blobs.  d_parent, d_blobs: h * w words each.
-void launch_blob_label(const uint16_t* d_labels, int h, int w, int* d_parent, uint32_t* d_blobs, unsigned* d_sums, unsigned* d_count, hipStream_t s);
-// d_blobs[p] = number of p's blob (0: background); d_table (nullable, one row per blob): every row initialised for launch_blob_stats
-void launch_blob_number(const int* d_numbers, uint32_t* d_blobs, const uint16_t* d_labels, int h, int w, anh_region* d_table, hipStream_t s);
-// area, bounding box, seeds (the flags of launch_detection_seeds counted per blob) and peak margin blended[label] - blended[0] of every blob,
-// by integer atomics; then `detected` (filtering: seeds > 0, else 1) and the peak as a float
-void launch_blob_stats(const uint32_t* d_blobs, const uint16_t* d_labels, const float* d_blended, int k, int h, int w, const uint8_t* d_flags,
-                       anh_region* d_table, uint32_t n_regions, bool filtering, hipStream_t s);
-// labels[p] = 0 where p's blob has no seed: one launch
-void launch_blob_filter(uint16_t* d_labels, const uint32_t* d_blobs, const anh_region* d_table, int64_t pixels, hipStream_t s);
-// ---- the same over n maps of one size lying back to back, [n][h][w]: the number of launches does not depend on n, and image i receives
-// exactly what the single-image launches give that map (blob numbers restart at 1 in every image) ----
-// what one launch can cover: h * w < 2^31 as above and n * (h and w rounded up to kBlobTile) < 2^32 pixels
+size_t blob_scan_blocks(int64_t pixels);   // words of d_sums per image
+// the limit of a stack as the batch entry points state it: h * w < 2^31 and n * (h and w rounded up to kBlobTile) < 2^32 pixels
 bool blob_batch_fits(int n, int h, int w);
-// flags [n][h][w] from d_blended [n][k][h][w] and d_labels [n][h][w]: launch_detection_seeds of every image, by one launch
-void launch_detection_seeds_batch(const float* d_blended, const uint16_t* d_labels, int k, int n, int h, int w, const double* d_det, uint8_t* d_flags, hipStream_t s);
-// d_sums: n * blob_scan_blocks(h * w) words; d_counts[i] = blobs of image i + 1.  d_parent, d_blobs: n * h * w words each.
-void launch_blob_label_batch(const uint16_t* d_labels, int n, int h, int w, int* d_parent, uint32_t* d_blobs, unsigned* d_sums, unsigned* d_counts, hipStream_t s);
+// what one labelling can cover: blob_batch_fits for n >= 2; a single map (n = 1) needs h * w < 2^31 alone
+bool blob_stack_fits(int n, int h, int w);
+// local, seam, flatten, scan, rank.  Afterwards d_counts[i] = blobs of image i + 1, d_blobs[p] = root(p) + 1 (0: background) and the
+// root's slot of d_parent holds the blob's number: launch_blob_number finishes d_blobs.  d_parent, d_blobs: n * h * w words each;
+// d_sums: n * blob_scan_blocks(h * w) words.
+void launch_blob_label(const uint16_t* d_labels, int n, int h, int w, int* d_parent, uint32_t* d_blobs, unsigned* d_sums, unsigned* d_counts, hipStream_t s);
+// d_blobs[p] = number of p's blob (0: background); d_table (nullable, one row per blob): every row initialised for launch_blob_stats.
 // d_row_offsets[i] = rows of the images before i (the host's exclusive sum of counts[i] - 1): image i's rows are d_table + d_row_offsets[i].
 // d_table == nullptr (then d_row_offsets is not read): the blob maps alone.
-void launch_blob_number_batch(const int* d_numbers, uint32_t* d_blobs, const uint16_t* d_labels, int n, int h, int w, anh_region* d_table,
-                              const unsigned long long* d_row_offsets, hipStream_t s);
-void launch_blob_stats_batch(const uint32_t* d_blobs, const uint16_t* d_labels, const float* d_blended, int k, int n, int h, int w, const uint8_t* d_flags,
-                             anh_region* d_table, const unsigned long long* d_row_offsets, uint32_t total_regions, bool filtering, hipStream_t s);
-void launch_blob_filter_batch(uint16_t* d_labels, const uint32_t* d_blobs, const anh_region* d_table, const unsigned long long* d_row_offsets, int n, int64_t pixels,
-                              hipStream_t s);
+void launch_blob_number(const int* d_numbers, uint32_t* d_blobs, const uint16_t* d_labels, int n, int h, int w, anh_region* d_table,
+                        const unsigned long long* d_row_offsets, hipStream_t s);
+// area, bounding box, seeds (the flags of launch_detection_seeds counted per blob) and peak margin blended[label] - blended[0] of every blob,
+// by integer atomics; then `detected` (filtering: seeds > 0, else 1) and the peak as a float
+void launch_blob_stats(const uint32_t* d_blobs, const uint16_t* d_labels, const float* d_blended, int k, int n, int h, int w, const uint8_t* d_flags,
+                       anh_region* d_table, const unsigned long long* d_row_offsets, uint32_t total_regions, bool filtering, hipStream_t s);
+// labels[p] = 0 where p's blob has no seed: one launch
+void launch_blob_filter(uint16_t* d_labels, const uint32_t* d_blobs, const anh_region* d_table, const unsigned long long* d_row_offsets, int n, int64_t pixels,
+                        hipStream_t s);
 // ---- scoring result maps against their ground truth (kernels_score.hip; annonet_infer_main.cpp:482-491, :202-272) ----
-// d_maps [2n][h][w] = [n truth maps ; n result maps] and d_blobs their blob maps (launch_blob_label_batch + launch_blob_number_batch);
+// d_maps [2n][h][w] = [n truth maps ; n result maps] and d_blobs their blob maps (launch_blob_label + launch_blob_number);
 // d_row_offsets: 2n values, the first vote row of every map (the host's exclusive sum of the labeller's counts: blobs + 1 = regions);
 // d_votes: one row of k + 1 words per region, CLEARED by the caller, as d_labelled [n] and d_pixel [n][k][k] are.  Integer atomics only.
 void launch_score_tally(const uint16_t* d_maps, const uint32_t* d_blobs, int n, int k, int h, int w, const unsigned long long* d_row_offsets, unsigned* d_votes,

@@ -16,8 +16,8 @@
 //   stats    area, bounding box, seed count, peak margin: integer atomics only (order-independent, bitwise reproducible), summed per
 //            wave and per workgroup (an LDS table keyed by blob number) before they touch global memory
 //
-// A stack of n maps of one size, [n][h][w], goes through the same steps with a number of launches that does not depend on n (the `_batch_`
-// kernels): the grid of every step covers n times the blocks of one map and no block straddles two images; parents, roots and blob
+// Every step works on a stack of n maps of one size, [n][h][w], with a number of launches that does not depend on n; one map is a stack
+// with n = 1.  The grid of every step covers n times the blocks of one map and no block straddles two images; parents, roots and blob
 // numbers stay plane-local (the numbers restart at 1 in every image, the scan has one workgroup per image); image i's table rows begin
 // at row_offsets[i], which the host sums from the counts.
 #include <hip/hip_runtime.h>
@@ -91,12 +91,15 @@ __device__ __forceinline__ void global_unite(int* parent, int a, int b) {
     }
 }
 
-// The bodies below take the map they work on and the index of their block WITHIN that map: the single-image kernels pass blockIdx.x, the
-// batched ones (`_batch_`) cut blockIdx.x into (image, block) and move the pointers to that image's plane.  Everything a body computes
-// is plane-local, so an image of a stack gets exactly the bits the single-image launch gives that map.
-__device__ __forceinline__ void blob_local_body(const uint16_t* labels, int* parent, int h, int w, int tiles_x, unsigned tile) {
+// Every kernel below cuts blockIdx.x ONCE into (image, block within the image) and moves its pointers to that image's plane; the addresses
+// add image * plane in 64 bits.  Everything computed after that is plane-local (parent values are linear indices within the plane), so an
+// image gets the same bits whatever stack it lies in, a stack of one included.  The grid of the two tile kernels covers n x tiles.
+__global__ __launch_bounds__(256) void blob_local_kernel(const uint16_t* labels, int* parent, int h, int w, int tiles_x, unsigned tiles) {
     __shared__ uint16_t lab[T + 1][T + 2];   // a frame of zeros above, left and right: label 0 never joins a blob
     __shared__ int par[T * T];
+    const unsigned image = blockIdx.x / tiles, tile = blockIdx.x - image * tiles;
+    const size_t at = (size_t)image * ((size_t)h * w);
+    labels += at; parent += at;
     const int tile_y = (int)(tile / (unsigned)tiles_x), tile_x = (int)(tile - (unsigned)tile_y * (unsigned)tiles_x);
     const int x0 = tile_x * T, y0 = tile_y * T;
     for (int i = threadIdx.x; i < (T + 1) * (T + 2); i += 256) (&lab[0][0])[i] = 0;
@@ -134,19 +137,13 @@ __device__ __forceinline__ void blob_local_body(const uint16_t* labels, int* par
         parent[(size_t)y * w + x] = out;
     }
 }
-__global__ __launch_bounds__(256) void blob_local_kernel(const uint16_t* labels, int* parent, int h, int w, int tiles_x) {
-    blob_local_body(labels, parent, h, w, tiles_x, blockIdx.x);
-}
-// the grid covers n x tiles; parent values stay plane-local linear indices, the addresses add image * plane in 64 bits
-__global__ __launch_bounds__(256) void blob_local_batch_kernel(const uint16_t* labels, int* parent, int h, int w, int tiles_x, unsigned tiles) {
-    const unsigned image = blockIdx.x / tiles;
-    const size_t at = (size_t)image * ((size_t)h * w);
-    blob_local_body(labels + at, parent + at, h, w, tiles_x, blockIdx.x - image * tiles);
-}
 
 // Neighbours are tested against the sides of the plane (nx, ny), never through the linear index: a seam neither wraps from a row's last
 // column to the next row's first nor, in a stack, runs from the last row of one image into the first row of the next.
-__device__ __forceinline__ void blob_seam_body(const uint16_t* labels, int* parent, int h, int w, int tiles_x, unsigned tile) {
+__global__ __launch_bounds__(128) void blob_seam_kernel(const uint16_t* labels, int* parent, int h, int w, int tiles_x, unsigned tiles) {
+    const unsigned image = blockIdx.x / tiles, tile = blockIdx.x - image * tiles;
+    const size_t at = (size_t)image * ((size_t)h * w);
+    labels += at; parent += at;
     const int tile_y = (int)(tile / (unsigned)tiles_x), tile_x = (int)(tile - (unsigned)tile_y * (unsigned)tiles_x);
     const int t = threadIdx.x;
     int ly, lx;
@@ -166,14 +163,6 @@ __device__ __forceinline__ void blob_seam_body(const uint16_t* labels, int* pare
         if (nx / T == tile_x && ny / T == tile_y) continue;   // the local pass has joined these
         if (labels[(size_t)ny * w + nx] == l) global_unite(parent, p, ny * w + nx);
     }
-}
-__global__ __launch_bounds__(128) void blob_seam_kernel(const uint16_t* labels, int* parent, int h, int w, int tiles_x) {
-    blob_seam_body(labels, parent, h, w, tiles_x, blockIdx.x);
-}
-__global__ __launch_bounds__(128) void blob_seam_batch_kernel(const uint16_t* labels, int* parent, int h, int w, int tiles_x, unsigned tiles) {
-    const unsigned image = blockIdx.x / tiles;
-    const size_t at = (size_t)image * ((size_t)h * w);
-    blob_seam_body(labels + at, parent + at, h, w, tiles_x, blockIdx.x - image * tiles);
 }
 
 // block-wide exclusive prefix sum over THREADS values; *total = their sum.  Every thread of the block calls it.
@@ -200,9 +189,13 @@ __device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* w
     return before + x - v;
 }
 
-// roots[p] = root(p) + 1 (0: background); sums[block] = number of roots among the block's 1024 pixels
-__device__ __forceinline__ void blob_flatten_body(const int* parent, uint32_t* roots, unsigned* sums, int64_t pixels, unsigned block) {
+// roots[p] = root(p) + 1 (0: background); sums[block] = number of roots among the block's 1024 pixels.
+// `per_image` = ceil(pixels / 1024) blocks per image: no block straddles two images; sums is [n][per_image]
+__global__ __launch_bounds__(256) void blob_flatten_kernel(const int* parent, uint32_t* roots, unsigned* sums, int64_t pixels, unsigned per_image) {
     __shared__ unsigned wave_sums[4];
+    const unsigned image = blockIdx.x / per_image, block = blockIdx.x - image * per_image;
+    const size_t at = (size_t)image * (size_t)pixels;
+    parent += at; roots += at; sums += (size_t)image * per_image;
     const int64_t base = (int64_t)block * kScanPixels + threadIdx.x * 4;
     unsigned mine = 0;
 #pragma unroll
@@ -219,39 +212,29 @@ __device__ __forceinline__ void blob_flatten_body(const int* parent, uint32_t* r
     (void)block_exclusive_scan<256>(mine, wave_sums, &total);
     if (threadIdx.x == 0) sums[block] = total;
 }
-__global__ __launch_bounds__(256) void blob_flatten_kernel(const int* parent, uint32_t* roots, unsigned* sums, int64_t pixels) {
-    blob_flatten_body(parent, roots, sums, pixels, blockIdx.x);
-}
-// `per_image` = ceil(pixels / 1024) blocks per image: no block straddles two images; sums is [n][per_image]
-__global__ __launch_bounds__(256) void blob_flatten_batch_kernel(const int* parent, uint32_t* roots, unsigned* sums, int64_t pixels, unsigned per_image) {
-    const unsigned image = blockIdx.x / per_image;
-    const size_t at = (size_t)image * (size_t)pixels;
-    blob_flatten_body(parent + at, roots + at, sums + (size_t)image * per_image, pixels, blockIdx.x - image * per_image);
-}
 
-// sums[i] -> sum of sums[0 .. i); *count = the total + 1 ("labels including the background one")
-__device__ __forceinline__ void blob_scan_sums_body(unsigned* sums, int n, unsigned* count) {
+// one workgroup per image, so the prefix sum restarts at every image: sums[image][i] -> sum of sums[image][0 .. i);
+// counts[image] = the image's total + 1 ("labels including the background one")
+__global__ __launch_bounds__(1024) void blob_scan_sums_kernel(unsigned* sums, int per_image, unsigned* counts) {
     __shared__ unsigned wave_sums[16];
+    sums += (size_t)blockIdx.x * per_image;
     unsigned carry = 0;
-    for (int base = 0; base < n; base += 1024) {
+    for (int base = 0; base < per_image; base += 1024) {
         const int i = base + (int)threadIdx.x;
-        const unsigned v = i < n ? sums[i] : 0u;
+        const unsigned v = i < per_image ? sums[i] : 0u;
         unsigned total;
         const unsigned before = block_exclusive_scan<1024>(v, wave_sums, &total);
-        if (i < n) sums[i] = carry + before;
+        if (i < per_image) sums[i] = carry + before;
         carry += total;
     }
-    if (threadIdx.x == 0) *count = carry + 1u;
-}
-__global__ __launch_bounds__(1024) void blob_scan_sums_kernel(unsigned* sums, int n, unsigned* count) { blob_scan_sums_body(sums, n, count); }
-// one workgroup per image: the prefix sum restarts at every image; counts[image] = that image's blobs + 1
-__global__ __launch_bounds__(1024) void blob_scan_sums_batch_kernel(unsigned* sums, int per_image, unsigned* counts) {
-    blob_scan_sums_body(sums + (size_t)blockIdx.x * per_image, per_image, counts + blockIdx.x);
+    if (threadIdx.x == 0) counts[blockIdx.x] = carry + 1u;
 }
 
-// every root's slot of parent[] receives the blob's number: 1 + the number of roots before it in raster order
-__device__ __forceinline__ void blob_rank_body(int* parent, const unsigned* sums, int64_t pixels, unsigned block) {
+// every root's slot of parent[] receives the blob's number: 1 + the number of roots before it in raster order OF ITS IMAGE
+__global__ __launch_bounds__(256) void blob_rank_kernel(int* parent, const unsigned* sums, int64_t pixels, unsigned per_image) {
     __shared__ unsigned wave_sums[4];
+    const unsigned image = blockIdx.x / per_image, block = blockIdx.x - image * per_image;
+    parent += (size_t)image * (size_t)pixels; sums += (size_t)image * per_image;
     const int64_t base = (int64_t)block * kScanPixels + threadIdx.x * 4;
     bool root[4];
     unsigned mine = 0;
@@ -267,15 +250,15 @@ __device__ __forceinline__ void blob_rank_body(int* parent, const unsigned* sums
     for (int j = 0; j < 4; ++j)
         if (root[j]) parent[base + j] = (int)++number;
 }
-__global__ __launch_bounds__(256) void blob_rank_kernel(int* parent, const unsigned* sums, int64_t pixels) { blob_rank_body(parent, sums, pixels, blockIdx.x); }
-// the numbers restart at 1 in every image
-__global__ __launch_bounds__(256) void blob_rank_batch_kernel(int* parent, const unsigned* sums, int64_t pixels, unsigned per_image) {
-    const unsigned image = blockIdx.x / per_image;
-    blob_rank_body(parent + (size_t)image * (size_t)pixels, sums + (size_t)image * per_image, pixels, blockIdx.x - image * per_image);
-}
 
 // blobs[p]: root(p) + 1 -> the blob's number.  table != nullptr: the root's thread writes the blob's row (14 words, padding included).
-__device__ __forceinline__ void blob_number_body(const int* numbers, uint32_t* blobs, const uint16_t* labels, anh_region* table, int64_t pixels, int w, unsigned block) {
+// row_offsets[image] = the number of rows of the images before it: image i's rows begin there (table == nullptr: never read)
+__global__ __launch_bounds__(256) void blob_number_kernel(const int* numbers, uint32_t* blobs, const uint16_t* labels, anh_region* table,
+                                                          const unsigned long long* row_offsets, int64_t pixels, int w, unsigned per_image) {
+    const unsigned image = blockIdx.x / per_image, block = blockIdx.x - image * per_image;
+    const size_t at = (size_t)image * (size_t)pixels;
+    numbers += at; blobs += at; labels += at;
+    if (table) table += row_offsets[image];
     const int64_t p = (int64_t)block * 256 + threadIdx.x;
     if (p >= pixels) return;
     const uint32_t r = blobs[p];
@@ -293,16 +276,6 @@ __device__ __forceinline__ void blob_number_body(const int* numbers, uint32_t* b
         row[12] = kPeakNone;
         row[13] = 0;
     }
-}
-__global__ __launch_bounds__(256) void blob_number_kernel(const int* numbers, uint32_t* blobs, const uint16_t* labels, anh_region* table, int64_t pixels, int w) {
-    blob_number_body(numbers, blobs, labels, table, pixels, w, blockIdx.x);
-}
-// row_offsets[image] = the number of rows of the images before it: image i's rows begin there (table == nullptr: never read)
-__global__ __launch_bounds__(256) void blob_number_batch_kernel(const int* numbers, uint32_t* blobs, const uint16_t* labels, anh_region* table,
-                                                                const unsigned long long* row_offsets, int64_t pixels, int w, unsigned per_image) {
-    const unsigned image = blockIdx.x / per_image;
-    const size_t at = (size_t)image * (size_t)pixels;
-    blob_number_body(numbers + at, blobs + at, labels + at, table ? table + row_offsets[image] : nullptr, pixels, w, blockIdx.x - image * per_image);
 }
 
 struct StatSlots {
@@ -340,10 +313,14 @@ __device__ __forceinline__ void stat_to_lds(StatSlots& s, anh_region* table, uns
     stat_to_global(table, b, area, seeds, left, top, right, bottom, peak);   // a crowded table: more blobs in this block than it holds
 }
 
-// the margin is computed in float exactly as det_seed_kernel computes `mine - clean`
-__device__ __forceinline__ void blob_stats_body(const uint32_t* blobs, const uint16_t* labels, const float* blended, int k, const uint8_t* flags,
-                                                anh_region* table, int64_t pixels, int w, unsigned block) {
+// the margin is computed in float exactly as det_seed_kernel computes `mine - clean`.
+// ceil(pixels / 4096) blocks per image, so a workgroup's LDS table is keyed by the blob numbers of ONE image; blended is [n][k][h][w]
+__global__ __launch_bounds__(256) void blob_stats_kernel(const uint32_t* blobs, const uint16_t* labels, const float* blended, int k, const uint8_t* flags,
+                                                         anh_region* table, const unsigned long long* row_offsets, int64_t pixels, int w, unsigned per_image) {
     __shared__ StatSlots s;
+    const unsigned image = blockIdx.x / per_image, block = blockIdx.x - image * per_image;
+    const size_t at = (size_t)image * (size_t)pixels;
+    blobs += at; labels += at; blended += at * (size_t)k; flags += at; table += row_offsets[image];
     for (int i = threadIdx.x; i < kStatSlots; i += 256) {
         s.key[i] = 0; s.area[i] = 0; s.seeds[i] = 0; s.peak[i] = 0;
         s.left[i] = INT_MAX; s.top[i] = INT_MAX; s.right[i] = -1; s.bottom[i] = -1;
@@ -390,17 +367,6 @@ __device__ __forceinline__ void blob_stats_body(const uint32_t* blobs, const uin
     for (int i = threadIdx.x; i < kStatSlots; i += 256)
         if (s.key[i]) stat_to_global(table, s.key[i], s.area[i], s.seeds[i], s.left[i], s.top[i], s.right[i], s.bottom[i], s.peak[i]);
 }
-__global__ __launch_bounds__(256) void blob_stats_kernel(const uint32_t* blobs, const uint16_t* labels, const float* blended, int k, const uint8_t* flags,
-                                                         anh_region* table, int64_t pixels, int w) {
-    blob_stats_body(blobs, labels, blended, k, flags, table, pixels, w, blockIdx.x);
-}
-// ceil(pixels / 4096) blocks per image, so a workgroup's LDS table is keyed by the blob numbers of ONE image; blended is [n][k][h][w]
-__global__ __launch_bounds__(256) void blob_stats_batch_kernel(const uint32_t* blobs, const uint16_t* labels, const float* blended, int k, const uint8_t* flags,
-                                                               anh_region* table, const unsigned long long* row_offsets, int64_t pixels, int w, unsigned per_image) {
-    const unsigned image = blockIdx.x / per_image;
-    const size_t at = (size_t)image * (size_t)pixels;
-    blob_stats_body(blobs + at, labels + at, blended + at * (size_t)k, k, flags + at, table + row_offsets[image], pixels, w, blockIdx.x - image * per_image);
-}
 
 __global__ __launch_bounds__(256) void blob_finish_kernel(anh_region* table, uint32_t n, int filtering) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -410,14 +376,8 @@ __global__ __launch_bounds__(256) void blob_finish_kernel(anh_region* table, uin
     row->detected = (uint16_t)((!filtering || row->seeds > 0) ? 1 : 0);
 }
 
-__global__ __launch_bounds__(256) void blob_filter_kernel(uint16_t* labels, const uint32_t* blobs, const anh_region* table, int64_t pixels) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= pixels) return;
-    const uint32_t b = blobs[p];
-    if (b != 0 && table[b - 1].seeds == 0) labels[p] = 0;
-}
-__global__ __launch_bounds__(256) void blob_filter_batch_kernel(uint16_t* labels, const uint32_t* blobs, const anh_region* table, const unsigned long long* row_offsets,
-                                                                int64_t pixels, unsigned per_image) {
+__global__ __launch_bounds__(256) void blob_filter_kernel(uint16_t* labels, const uint32_t* blobs, const anh_region* table, const unsigned long long* row_offsets,
+                                                          int64_t pixels, unsigned per_image) {
     const unsigned image = blockIdx.x / per_image;
     const int64_t p = (int64_t)(blockIdx.x - image * per_image) * 256 + threadIdx.x;
     if (p >= pixels) return;
@@ -432,81 +392,51 @@ unsigned blocks_of(int64_t pixels, int per_block) { return (unsigned)((pixels + 
 
 size_t blob_scan_blocks(int64_t pixels) { return (size_t)blocks_of(pixels, kScanPixels); }
 
-void launch_blob_label(const uint16_t* d_labels, int h, int w, int* d_parent, uint32_t* d_blobs, unsigned* d_sums, unsigned* d_count, hipStream_t s) {
-    const int64_t pixels = (int64_t)h * w;
-    const int tiles_x = (w + T - 1) / T, tiles_y = (h + T - 1) / T;
-    const unsigned tiles = (unsigned)((int64_t)tiles_x * tiles_y), blocks = blocks_of(pixels, kScanPixels);
-    hipLaunchKernelGGL(blob_local_kernel, dim3(tiles), dim3(256), 0, s, d_labels, d_parent, h, w, tiles_x);
-    if (tiles > 1) hipLaunchKernelGGL(blob_seam_kernel, dim3(tiles), dim3(128), 0, s, d_labels, d_parent, h, w, tiles_x);
-    hipLaunchKernelGGL(blob_flatten_kernel, dim3(blocks), dim3(256), 0, s, d_parent, d_blobs, d_sums, pixels);
-    hipLaunchKernelGGL(blob_scan_sums_kernel, dim3(1), dim3(1024), 0, s, d_sums, (int)blocks, d_count);
-    hipLaunchKernelGGL(blob_rank_kernel, dim3(blocks), dim3(256), 0, s, d_parent, d_sums, pixels);
-    HIP_CHECK(hipGetLastError());
-}
-
-void launch_blob_number(const int* d_numbers, uint32_t* d_blobs, const uint16_t* d_labels, int h, int w, anh_region* d_table, hipStream_t s) {
-    const int64_t pixels = (int64_t)h * w;
-    hipLaunchKernelGGL(blob_number_kernel, dim3(blocks_of(pixels, 256)), dim3(256), 0, s, d_numbers, d_blobs, d_labels, d_table, pixels, w);
-    HIP_CHECK(hipGetLastError());
-}
-
-void launch_blob_stats(const uint32_t* d_blobs, const uint16_t* d_labels, const float* d_blended, int k, int h, int w, const uint8_t* d_flags,
-                       anh_region* d_table, uint32_t n_regions, bool filtering, hipStream_t s) {
-    if (n_regions == 0) return;
-    const int64_t pixels = (int64_t)h * w;
-    hipLaunchKernelGGL(blob_stats_kernel, dim3(blocks_of(pixels, kStatPixels)), dim3(256), 0, s, d_blobs, d_labels, d_blended, k, d_flags, d_table, pixels, w);
-    hipLaunchKernelGGL(blob_finish_kernel, dim3((n_regions + 255) / 256), dim3(256), 0, s, d_table, n_regions, filtering ? 1 : 0);
-    HIP_CHECK(hipGetLastError());
-}
-
-void launch_blob_filter(uint16_t* d_labels, const uint32_t* d_blobs, const anh_region* d_table, int64_t pixels, hipStream_t s) {
-    hipLaunchKernelGGL(blob_filter_kernel, dim3(blocks_of(pixels, 256)), dim3(256), 0, s, d_labels, d_blobs, d_table, pixels);
-    HIP_CHECK(hipGetLastError());
-}
-
-// ---- n maps of one size back to back, [n][h][w]: the same launches whatever n is ----
+// The limit of one labelling: h * w < 2^31 for every plane, and for a stack of two or more maps the tile-padded n * h * w < 2^32 as well.
+// (For n = 1 the first alone holds, and every grid below is the grid of that one map.)
 bool blob_batch_fits(int n, int h, int w) {
     if (n < 1 || h < 1 || w < 1 || (int64_t)h * w >= ((int64_t)1 << 31)) return false;
     const int64_t tiles = (int64_t)((w + T - 1) / T) * ((h + T - 1) / T);
     return (int64_t)n * tiles * (T * T) < ((int64_t)1 << 32);   // the widest launch has one thread per pixel of the tile-padded stack
 }
+bool blob_stack_fits(int n, int h, int w) { return n == 1 ? h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31) : blob_batch_fits(n, h, w); }
 
-void launch_blob_label_batch(const uint16_t* d_labels, int n, int h, int w, int* d_parent, uint32_t* d_blobs, unsigned* d_sums, unsigned* d_counts, hipStream_t s) {
-    ANH_REQUIRE(blob_batch_fits(n, h, w), "blob labelling of a stack: too many pixels for one launch");
+void launch_blob_label(const uint16_t* d_labels, int n, int h, int w, int* d_parent, uint32_t* d_blobs, unsigned* d_sums, unsigned* d_counts, hipStream_t s) {
+    ANH_REQUIRE(blob_stack_fits(n, h, w), "blob labelling of a stack: too many pixels for one launch");
     const int64_t pixels = (int64_t)h * w;
     const int tiles_x = (w + T - 1) / T, tiles_y = (h + T - 1) / T;
     const unsigned tiles = (unsigned)((int64_t)tiles_x * tiles_y), blocks = blocks_of(pixels, kScanPixels);
-    hipLaunchKernelGGL(blob_local_batch_kernel, dim3(tiles * (unsigned)n), dim3(256), 0, s, d_labels, d_parent, h, w, tiles_x, tiles);
-    if (tiles > 1) hipLaunchKernelGGL(blob_seam_batch_kernel, dim3(tiles * (unsigned)n), dim3(128), 0, s, d_labels, d_parent, h, w, tiles_x, tiles);
-    hipLaunchKernelGGL(blob_flatten_batch_kernel, dim3(blocks * (unsigned)n), dim3(256), 0, s, d_parent, d_blobs, d_sums, pixels, blocks);
-    hipLaunchKernelGGL(blob_scan_sums_batch_kernel, dim3((unsigned)n), dim3(1024), 0, s, d_sums, (int)blocks, d_counts);
-    hipLaunchKernelGGL(blob_rank_batch_kernel, dim3(blocks * (unsigned)n), dim3(256), 0, s, d_parent, d_sums, pixels, blocks);
+    hipLaunchKernelGGL(blob_local_kernel, dim3(tiles * (unsigned)n), dim3(256), 0, s, d_labels, d_parent, h, w, tiles_x, tiles);
+    if (tiles > 1) hipLaunchKernelGGL(blob_seam_kernel, dim3(tiles * (unsigned)n), dim3(128), 0, s, d_labels, d_parent, h, w, tiles_x, tiles);
+    hipLaunchKernelGGL(blob_flatten_kernel, dim3(blocks * (unsigned)n), dim3(256), 0, s, d_parent, d_blobs, d_sums, pixels, blocks);
+    hipLaunchKernelGGL(blob_scan_sums_kernel, dim3((unsigned)n), dim3(1024), 0, s, d_sums, (int)blocks, d_counts);
+    hipLaunchKernelGGL(blob_rank_kernel, dim3(blocks * (unsigned)n), dim3(256), 0, s, d_parent, d_sums, pixels, blocks);
     HIP_CHECK(hipGetLastError());
 }
 
-void launch_blob_number_batch(const int* d_numbers, uint32_t* d_blobs, const uint16_t* d_labels, int n, int h, int w, anh_region* d_table,
-                              const unsigned long long* d_row_offsets, hipStream_t s) {
+void launch_blob_number(const int* d_numbers, uint32_t* d_blobs, const uint16_t* d_labels, int n, int h, int w, anh_region* d_table,
+                        const unsigned long long* d_row_offsets, hipStream_t s) {
     const int64_t pixels = (int64_t)h * w;
     const unsigned per_image = blocks_of(pixels, 256);
-    hipLaunchKernelGGL(blob_number_batch_kernel, dim3(per_image * (unsigned)n), dim3(256), 0, s, d_numbers, d_blobs, d_labels, d_table, d_row_offsets, pixels, w, per_image);
+    hipLaunchKernelGGL(blob_number_kernel, dim3(per_image * (unsigned)n), dim3(256), 0, s, d_numbers, d_blobs, d_labels, d_table, d_row_offsets, pixels, w, per_image);
     HIP_CHECK(hipGetLastError());
 }
 
-void launch_blob_stats_batch(const uint32_t* d_blobs, const uint16_t* d_labels, const float* d_blended, int k, int n, int h, int w, const uint8_t* d_flags,
-                             anh_region* d_table, const unsigned long long* d_row_offsets, uint32_t total_regions, bool filtering, hipStream_t s) {
+void launch_blob_stats(const uint32_t* d_blobs, const uint16_t* d_labels, const float* d_blended, int k, int n, int h, int w, const uint8_t* d_flags,
+                       anh_region* d_table, const unsigned long long* d_row_offsets, uint32_t total_regions, bool filtering, hipStream_t s) {
     if (total_regions == 0) return;
     const int64_t pixels = (int64_t)h * w;
     const unsigned per_image = blocks_of(pixels, kStatPixels);
-    hipLaunchKernelGGL(blob_stats_batch_kernel, dim3(per_image * (unsigned)n), dim3(256), 0, s, d_blobs, d_labels, d_blended, k, d_flags, d_table, d_row_offsets, pixels, w,
+    hipLaunchKernelGGL(blob_stats_kernel, dim3(per_image * (unsigned)n), dim3(256), 0, s, d_blobs, d_labels, d_blended, k, d_flags, d_table, d_row_offsets, pixels, w,
                        per_image);
     hipLaunchKernelGGL(blob_finish_kernel, dim3((total_regions + 255) / 256), dim3(256), 0, s, d_table, total_regions, filtering ? 1 : 0);   // the rows lie back to back
     HIP_CHECK(hipGetLastError());
 }
 
-void launch_blob_filter_batch(uint16_t* d_labels, const uint32_t* d_blobs, const anh_region* d_table, const unsigned long long* d_row_offsets, int n, int64_t pixels,
-                              hipStream_t s) {
+void launch_blob_filter(uint16_t* d_labels, const uint32_t* d_blobs, const anh_region* d_table, const unsigned long long* d_row_offsets, int n, int64_t pixels,
+                        hipStream_t s) {
     const unsigned per_image = blocks_of(pixels, 256);
-    hipLaunchKernelGGL(blob_filter_batch_kernel, dim3(per_image * (unsigned)n), dim3(256), 0, s, d_labels, d_blobs, d_table, d_row_offsets, pixels, per_image);
+    hipLaunchKernelGGL(blob_filter_kernel, dim3(per_image * (unsigned)n), dim3(256), 0, s, d_labels, d_blobs, d_table, d_row_offsets, pixels, per_image);
     HIP_CHECK(hipGetLastError());
 }
 

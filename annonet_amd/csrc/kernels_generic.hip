@@ -1816,10 +1816,15 @@ __global__ __launch_bounds__(256) void labels_from_logits_kernel(const float* lo
 // transposed = 1 (ANH_DET_SEED_REFERENCE_ORDER=1): the reference stores the seed as point(r, c) (annonet_infer.cpp:210) and looks the
 //   blob up at (point.y(), point.x()) = (c, r) (:222): the seed marks the blob that holds the TRANSPOSED pixel.  Out-of-range transposed
 //   positions (non-square images: undefined behaviour in the reference) are dropped.  flags must be zero on entry.
+// Images lie back to back: labels and flags [n][pixels], blended [n][k][pixels].  `per_image` blocks serve one image: a block cuts
+// blockIdx.x into (image, block) once and strides through that image's plane alone, the transposed lookup included.
 __global__ __launch_bounds__(256) void det_seed_kernel(const float* blended, const uint16_t* labels, int k, int64_t pixels, const double* det, uint8_t* flags,
-                                                       int transposed, int h, int w) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < pixels; p += stride) {
+                                                       int transposed, int h, int w, unsigned per_image) {
+    const unsigned image = blockIdx.x / per_image, block = blockIdx.x - image * per_image;
+    const size_t at = (size_t)image * (size_t)pixels;
+    blended += at * (size_t)k; labels += at; flags += at;
+    const int64_t stride = (int64_t)per_image * blockDim.x;
+    for (int64_t p = (int64_t)block * blockDim.x + threadIdx.x; p < pixels; p += stride) {
         const uint16_t lab = labels[p];
         uint8_t f = 0;
         if (lab != 0 && lab != ANH_LABEL_IGNORE && lab < k) {
@@ -1830,27 +1835,6 @@ __global__ __launch_bounds__(256) void det_seed_kernel(const float* blended, con
         else if (f) {
             const int64_t r = p / w, c = p - r * w;
             if (c < h && r < w) flags[c * w + r] = 1;
-        }
-    }
-}
-
-// the same over images lying back to back: labels and flags [n][pixels], blended [n][k][pixels]; total = n * pixels
-__global__ __launch_bounds__(256) void det_seed_batch_kernel(const float* blended, const uint16_t* labels, int k, int64_t pixels, int64_t total, const double* det,
-                                                             uint8_t* flags, int transposed, int h, int w) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += stride) {
-        const int64_t image = q / pixels, p = q - image * pixels;
-        const float* planes = blended + (size_t)image * k * pixels;
-        const uint16_t lab = labels[q];
-        uint8_t f = 0;
-        if (lab != 0 && lab != ANH_LABEL_IGNORE && lab < k) {
-            const float clean = planes[p], mine = planes[(size_t)lab * pixels + p];
-            if ((double)(mine - clean) > det[lab] - det[0]) f = 1;
-        }
-        if (!transposed) flags[q] = f;
-        else if (f) {
-            const int64_t r = p / w, c = p - r * w;
-            if (c < h && r < w) flags[image * pixels + c * w + r] = 1;
         }
     }
 }
@@ -1911,10 +1895,7 @@ int run_detection_filter(const float* d_blended, uint16_t* d_labels, int k, int 
     const int64_t pixels = (int64_t)h * w;
     if (pixels == 0) return 0;
     const int blocks = (int)std::min<int64_t>((pixels + 255) / 256, 256 * 16);
-    static const int reference_order = getenv("ANH_DET_SEED_REFERENCE_ORDER") ? atoi(getenv("ANH_DET_SEED_REFERENCE_ORDER")) : 0;
-    if (reference_order) HIP_CHECK(hipMemsetAsync(d_flags, 0, (size_t)pixels, s));
-    hipLaunchKernelGGL(det_seed_kernel, dim3(blocks), dim3(256), 0, s, d_blended, d_labels, k, pixels, d_det, d_flags, reference_order, h, w);
-    HIP_CHECK(hipGetLastError());
+    launch_detection_seeds(d_blended, d_labels, k, 1, h, w, d_det, d_flags, s);
     int rounds = 0;
     const dim3 grid((unsigned)((w + 31) / 32), (unsigned)((h + 31) / 32));
     for (int round = 0;; ++round) {
@@ -1933,26 +1914,15 @@ int run_detection_filter(const float* d_blended, uint16_t* d_labels, int k, int 
     return rounds;
 }
 
-// The seed launch of run_detection_filter on its own (the region table counts these flags per blob, kernels_blobs.hip).
-void launch_detection_seeds(const float* d_blended, const uint16_t* d_labels, int k, int h, int w, const double* d_det, uint8_t* d_flags, hipStream_t s) {
+// The seed launch of run_detection_filter on its own, for n images lying back to back by ONE launch (the region table counts these flags
+// per blob, kernels_blobs.hip).  Every image's flags are those of the image alone: the same float subtraction and double comparison per pixel.
+void launch_detection_seeds(const float* d_blended, const uint16_t* d_labels, int k, int n, int h, int w, const double* d_det, uint8_t* d_flags, hipStream_t s) {
     const int64_t pixels = (int64_t)h * w;
-    if (pixels == 0) return;
-    const int blocks = (int)std::min<int64_t>((pixels + 255) / 256, 256 * 16);
+    if (pixels * n == 0) return;
+    const unsigned per_image = (unsigned)std::min<int64_t>((pixels + 255) / 256, 256 * 16);
     static const int reference_order = getenv("ANH_DET_SEED_REFERENCE_ORDER") ? atoi(getenv("ANH_DET_SEED_REFERENCE_ORDER")) : 0;
-    if (reference_order) HIP_CHECK(hipMemsetAsync(d_flags, 0, (size_t)pixels, s));
-    hipLaunchKernelGGL(det_seed_kernel, dim3(blocks), dim3(256), 0, s, d_blended, d_labels, k, pixels, d_det, d_flags, reference_order, h, w);
-    HIP_CHECK(hipGetLastError());
-}
-
-// ... of n images lying back to back by ONE launch: every image's flags are those of launch_detection_seeds on that image alone (the
-// same float subtraction and double comparison per pixel; the transposed lookup stays inside the image's own plane)
-void launch_detection_seeds_batch(const float* d_blended, const uint16_t* d_labels, int k, int n, int h, int w, const double* d_det, uint8_t* d_flags, hipStream_t s) {
-    const int64_t pixels = (int64_t)h * w, total = pixels * n;
-    if (total == 0) return;
-    const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 16);
-    static const int reference_order = getenv("ANH_DET_SEED_REFERENCE_ORDER") ? atoi(getenv("ANH_DET_SEED_REFERENCE_ORDER")) : 0;
-    if (reference_order) HIP_CHECK(hipMemsetAsync(d_flags, 0, (size_t)total, s));
-    hipLaunchKernelGGL(det_seed_batch_kernel, dim3(blocks), dim3(256), 0, s, d_blended, d_labels, k, pixels, total, d_det, d_flags, reference_order, h, w);
+    if (reference_order) HIP_CHECK(hipMemsetAsync(d_flags, 0, (size_t)(pixels * n), s));
+    hipLaunchKernelGGL(det_seed_kernel, dim3(per_image * (unsigned)n), dim3(256), 0, s, d_blended, d_labels, k, pixels, d_det, d_flags, reference_order, h, w, per_image);
     HIP_CHECK(hipGetLastError());
 }
 

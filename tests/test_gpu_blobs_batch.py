@@ -1,9 +1,10 @@
-"""Connected blobs over a stack of label maps, the batched kernels alone (anh_label_blobs_batch_device, anh_regions_batch_device): every
+"""Connected blobs over a stack of label maps, the blob kernels alone (anh_label_blobs_batch_device, anh_regions_batch_device): every
 image of a stack [n,H,W] gets the count, the blob map, the table rows and the filtered map that tests/blobs_ref.py gives that image
 alone, and, bit for bit, what the single-image calls return for it.  The shapes sit where a batched form can go wrong: planes of 1023,
 1024, 1025, 4095 and 4096 pixels (the 1024-pixel blocks of flatten / rank and the 4096-pixel blocks of the statistics launch must not
 straddle two images), one row, one column, several 32 x 32 tiles with ragged edges.  Blob maps are prefilled with 0xA5 so that an
-element no kernel writes shows."""
+element no kernel writes shows.  A single map is a stack of one on the same path: the last test runs single maps between stacks on one
+handle, so that every call finds the shared scratch laid out for another n and another size."""
 import numpy as np
 import pytest
 
@@ -205,3 +206,58 @@ def test_one_stack_twice_gives_the_same_bits():
     first = aa.label_blobs_batch(lab, prefill=0xA5)
     second = aa.label_blobs_batch(lab, prefill=0x00)
     assert first[1] == second[1] and first[0].tobytes() == second[0].tobytes()
+
+
+# ---- one handle, calls whose reservations lay the shared scratch out differently ----
+def layout_cases():
+    """[(label maps [n,H,W], planes [n,K,H,W], stacked)] in call order: a stack of 3, then single maps of 2 x 3 ragged tiles, of one tile
+    (no seam launch) and of one pixel, then the stack again.  Read-only, computed once."""
+    if "layout" not in _cache:
+        big = (40, 70)
+        first = np.stack([br.pattern("random", big), br.pattern("random_wide_values", big), br.smooth_map(big, 3)])
+        singles = [br.pattern("random", (33, 65))[None], br.pattern("random_wide_values", (32, 32))[None], np.ones((1, 1, 1), np.uint16)]
+        out = []
+        for i, (lab, stacked) in enumerate([(first, True)] + [(s, False) for s in singles]):
+            planes = planes_for(lab.shape[0], lab.shape[1:], 100 + i)
+            if lab.shape[1:] == (1, 1):
+                planes = np.array([0.0, 5.0, 0.0], np.float32).reshape(1, K, 1, 1)      # a margin above its level: the pixel's blob is kept
+            lab.setflags(write=False)
+            planes.setflags(write=False)
+            out.append((lab, planes, stacked))
+        _cache["layout"] = out + out[:1]
+    return _cache["layout"]
+
+
+def test_layout_cases_are_what_they_claim():
+    cases = layout_cases()
+    assert [c[0].shape for c in cases] == [(3, 40, 70), (1, 33, 65), (1, 32, 32), (1, 1, 1), (3, 40, 70)]
+    kept = removed = 0
+    for lab, planes, _ in cases:
+        for i in range(lab.shape[0]):
+            table, _, count = br.region_table(lab[i], planes[i], LEVELS)
+            assert count >= 2                                     # no map is all background
+            kept += int((table["seeds"] > 0).sum())
+            removed += int((table["seeds"] == 0).sum())
+            if lab[i].size > 1:
+                assert (table["seeds"] > 0).any() and (table["seeds"] == 0).any()      # the filter keeps a blob and removes one in every map
+    assert kept and removed
+
+
+@pytest.mark.parametrize("levels", [LEVELS, None], ids=["levels", "no_levels"])
+def test_single_maps_between_stacks_on_one_handle(levels):
+    """A single-image call is a stack of one on the scratch the previous call laid out for another n and another size: an offset or a
+    count left by that layout must not be read."""
+    net = aa.RuntimeNet(aa.net_config(1, 3, 3, 0.25, 4, aa.ANH_FP32))
+    positive = levels is not None
+    for step, (lab, planes, stacked) in enumerate(layout_cases()):
+        if stacked:
+            tables, blobs, after = aa.regions_batch(lab, planes, detection_levels=levels, apply_filter=True, prefill=0xA5, net=net)
+        else:
+            t, b, a = aa.regions(lab[0], planes[0], detection_levels=levels, apply_filter=True, prefill=0xA5, net=net)
+            tables, blobs, after = [t], b[None], a[None]
+        for i in range(lab.shape[0]):
+            want, want_blobs, want_count = br.region_table(lab[i], planes[i], levels)
+            assert len(tables[i]) == want_count - 1, (step, i)
+            np.testing.assert_array_equal(blobs[i], want_blobs, err_msg="step %d image %d" % (step, i))
+            br.assert_table_equal(tables[i], want)
+            np.testing.assert_array_equal(after[i], br.filtered(lab[i], want_blobs, want) if positive else lab[i], err_msg="step %d image %d" % (step, i))
