@@ -14,6 +14,7 @@
 #include "bnacc.h"
 #include "common.h"
 #include "kernels.h"
+#include "tilewalk.h"
 
 namespace anh {
 namespace {
@@ -590,8 +591,8 @@ __global__ __launch_bounds__(256) void stem_forward_kernel(ConvArgs a, int tiles
     __shared__ __attribute__((aligned(16))) float ws[ROWS * 32];
     const int tid = threadIdx.x;
     const int tile = blockIdx.x;
-    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
-    const int x0 = tx * 32, y0 = ty * 8;
+    const TilePos t = tile_pos(tile, tiles_x, tiles_y);
+    const int x0 = t.tx * 32, y0 = t.ty * 8, n = t.n;
     for (int i = tid; i < ROWS * 32; i += 256) ws[i] = a.w_f32[i];
     for (int i = tid; i < PH * PW * CIN; i += 256) {
         const int c = i % CIN, px = (i / CIN) % PW, py = i / (CIN * PW);
@@ -751,8 +752,8 @@ __global__ __launch_bounds__(320) void wgrad_stem_kernel(WgradArgs a, int tiles_
     for (int j = 0; j < 8; ++j) acc[j] = 0.f;
 
     for (int tile = blockIdx.x; tile < total_tiles; tile += splits) {
-        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
-        const int x0 = tx * kStemTW, y0 = ty * kStemTH;
+        const TilePos t = tile_pos(tile, tiles_x, tiles_y);
+        const int x0 = t.tx * kStemTW, y0 = t.ty * kStemTH, n = t.n;
         __syncthreads();
         for (int i = tid; i < kStemPH * kStemPW * CIN; i += nthreads) {
             const int c = i % CIN, px = (i / CIN) % kStemPW, py = i / (CIN * kStemPW);
@@ -796,8 +797,7 @@ bool stem_wgrad_ok(const WgradArgs& a) {
            a.h_in == a.h_out && a.w_in == a.w_out;
 }
 int stem_wgrad_splits(const WgradArgs& a) {
-    const int tiles = ((a.w_out + kStemTW - 1) / kStemTW) * ((a.h_out + kStemTH - 1) / kStemTH) * a.n;
-    return std::max(1, std::min(tiles, 1024));
+    return std::max(1, std::min(tiles_stem(a.h_out, a.w_out, a.n).total, 1024));
 }
 
 void wgrad_plan(const WgradArgs& a, int& splits, int64_t& pix_per_split, int& n_ci_tiles, int& n_co_tiles) {
@@ -1941,8 +1941,9 @@ void launch_conv_generic(const ConvArgs& a, hipStream_t s) {
         return;
     }
     if (stem_forward_ok(a)) {
-        const int tiles_x = (a.w_out + 31) / 32, tiles_y = (a.h_out + 7) / 8;
-        const dim3 grid((unsigned)(tiles_x * tiles_y * a.n));
+        const TileCounts t = tiles_stem(a.h_out, a.w_out, a.n);
+        const int tiles_x = t.tiles_x, tiles_y = t.tiles_y;
+        const dim3 grid((unsigned)t.total);
         const bool bf = a.out_dtype == DT_BF16;
         if (a.c_red == 3) {
             if (bf) hipLaunchKernelGGL((stem_forward_kernel<3, bf16>), grid, dim3(256), 0, s, a, tiles_x, tiles_y);
@@ -1981,8 +1982,8 @@ void launch_wgrad_generic(const WgradArgs& a, hipStream_t s) {
         const int splits = stem_wgrad_splits(a);
         const int64_t nw = (int64_t)a.k * a.k * a.c_in * a.c_out;
         ANH_REQUIRE((int64_t)splits * nw <= a.partials_capacity, "wgrad scratch too small");
-        const int tiles_x = (a.w_out + kStemTW - 1) / kStemTW, tiles_y = (a.h_out + kStemTH - 1) / kStemTH;
-        const int total = tiles_x * tiles_y * a.n;
+        const TileCounts t = tiles_stem(a.h_out, a.w_out, a.n);
+        const int tiles_x = t.tiles_x, tiles_y = t.tiles_y, total = t.total;
         const bool bf = a.dy_dtype == DT_BF16;
         if (a.c_in == 3) {
             if (bf) hipLaunchKernelGGL((wgrad_stem_kernel<3, bf16>), dim3(splits), dim3(320), 0, s, a, tiles_x, tiles_y, total, splits);

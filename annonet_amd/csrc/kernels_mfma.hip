@@ -24,6 +24,7 @@
 #include "bnacc.h"
 #include "common.h"
 #include "kernels.h"
+#include "tilewalk.h"
 
 namespace anh {
 
@@ -508,8 +509,8 @@ __global__ __launch_bounds__(256, (NT == 4 ? 1 : 2)) void conv3x3s1_mfma_kernel(
     const int half = lane >> 5, col = lane & 31;
     const int tile = blockIdx.x;
     const int co_base = blockIdx.y * C_OUT;  // 128-channel layers are split over two workgroups of 64 channels (occupancy)
-    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
-    const int x0 = tx * TW, y0 = ty * TH;
+    const TilePos t = tile_pos(tile, tiles_x, tiles_y);
+    const int x0 = t.tx * TW, y0 = t.ty * TH, n = t.n;
     const int H = a.h_out, W = a.w_out;  // stride 1, pad 1: input and output planes have the same size
     const int c_red = a.c_red;
     const bf16* wsrc = reinterpret_cast<const bf16*>(a.w_bf16);
@@ -575,9 +576,12 @@ __global__ __launch_bounds__(256, (NT == 4 ? 1 : 2)) void conv3x3s1_mfma_kernel(
     }
 }
 
+// which kernel a supported 3x3 layer takes, and its launch geometry (conv_plan)
+struct ConvPlan { int geo /*0 s1, 1 down, 2 up*/, nt, tiles_x, tiles_y, flip, form /*0 classic one-tile kernels, 2 warp-specialised*/, grid_x, groups; };
+
 template <int NT, int TAPS>
-void launch_s1(const ConvArgs& a, hipStream_t s) {
-    const int tiles_x = (a.w_out + TW - 1) / TW, tiles_y = (a.h_out + TH - 1) / TH;
+void launch_s1(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    const int tiles_x = p.tiles_x, tiles_y = p.tiles_y;
     const dim3 grid((unsigned)(tiles_x * tiles_y * a.n), (unsigned)(a.c_out / (NT * 32))), block(256);
     const size_t lds = X_BYTES + (size_t)TAPS * NT * 32 * 64;
     const int flip = a.gather;  // backward-data of a stride-1 conv = the same conv with the taps mirrored
@@ -771,8 +775,8 @@ __global__ __launch_bounds__(256, 1) void wgrad3x3_mfma_kernel(WgParams a, int t
     unsigned pok = 0, tok = 0;
     const size_t p_plane = (size_t)a.patch.h * a.patch.w * a.patch.c, t_plane = (size_t)a.tile.h * a.tile.w * a.tile.c;  // < 2^31 elements (host check)
     auto fetch = [&](int tile) {
-        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
-        const int x0 = tx * TW, y0 = ty * TH;
+        const TilePos t = tile_pos(tile, tiles_x, tiles_y);
+        const int x0 = t.tx * TW, y0 = t.ty * TH, n = t.n;
         const bf16* pa = a.patch.a + (size_t)n * p_plane;
         const bf16* pb = KP == SRC_ACT2 ? a.patch.b + (size_t)n * p_plane : nullptr;
         const int yb = STRIDE * y0 + G::ORIGIN, xb = STRIDE * x0 + G::ORIGIN;
@@ -888,15 +892,12 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_ws_kernel(WgParams a, int til
     }
     __syncthreads();
 
-    // XCD bands (splits_all bit 30; ANH_WGRAD_XCD_BANDS): as conv3x3_ws — the workgroups of one XCD (split & 7: gridDim.x is a multiple of
-    // 8, so every slab / channel group of a split sits on that XCD too) walk one contiguous eighth of the tile list together, so the halo
-    // rows and columns neighbouring patches share are re-read from that XCD's L2.  Which tiles a split sums changes with it (fp32 partials
-    // in another — still fixed — order).
-    const int wbands = (splits_all >> 30) & 1, n_splits = splits_all & 0x3fffffff;
-    const int band_len = (total_tiles_all + 7) >> 3;
-    const int splits = wbands ? n_splits >> 3 : n_splits;                                                  // this split's step through the list
-    const int total_tiles = wbands ? min(total_tiles_all, ((split & 7) + 1) * band_len) : total_tiles_all;   // ... and its end
-    int tile = wbands ? (split & 7) * band_len + (split >> 3) : split, it = 0;
+    // XCD bands (splits_all bit 30; ANH_WGRAD_XCD_BANDS): the band walk of tilewalk.h, as conv3x3_ws — gridDim.x is a multiple of 8, so
+    // every slab / channel group of a split sits on the split's XCD too.  Which tiles a split sums changes with it (fp32 partials in
+    // another — still fixed — order).
+    const TileWalk walk = tile_walk(split, splits_all & 0x3fffffff, total_tiles_all, (splits_all >> 30) & 1);
+    const int splits = walk.step, total_tiles = walk.end;
+    int tile = walk.first, it = 0;
     if (producer) {
         // per-channel bn constants of the patch side: this thread's 8 channels, in registers
         float psa[8], pta[8], psb[8], ptb[8];
@@ -940,8 +941,8 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_ws_kernel(WgParams a, int til
             }
         };
         auto fetch = [&](Regs& R, int tile_) __attribute__((always_inline)) {
-            const int tx = tile_ % tiles_x, ty = (tile_ / tiles_x) % tiles_y, n = tile_ / (tiles_x * tiles_y);
-            const int x0 = tx * TW, y0 = ty * TH;
+            const TilePos t = tile_pos(tile_, tiles_x, tiles_y);
+            const int x0 = t.tx * TW, y0 = t.ty * TH, n = t.n;
             const bf16* pa = a.patch.a + (size_t)n * p_plane;
             const bf16* pb = KP == SRC_ACT2 ? a.patch.b + (size_t)n * p_plane : nullptr;
             const int yb = STRIDE * y0 + ORIGIN, xb = STRIDE * x0 + ORIGIN;
@@ -1320,15 +1321,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a, int tile
     const int co_base = blockIdx.y * C_OUT;
     const int H = a.h_in, W = a.w_in, c_red = a.c_red;
     const int n_slabs = c_red >> 5, n_tiles_all = tiles_x * tiles_y * a.n;
-    // Which tiles this workgroup walks.  Plain: tile blockIdx.x, then every gridDim.x-th.  XCD bands (`bands`; gridDim.x a multiple of 8):
-    // the hardware deals workgroups round-robin over the 8 XCDs (observed, MI355X_MICROARCH.md: blocks b and b + 8 share one — used for
-    // speed only, any placement gives the same result), so the workgroups with equal blockIdx.x & 7 take ONE contiguous eighth of the
-    // row-major tile list and step through it together, gridDim.x / 8 consecutive tiles at a time: the halo rows and columns a patch
-    // shares with its neighbours are then re-read from that XCD's own L2 instead of once per XCD from the memory side.
-    const int band_len = (n_tiles_all + 7) >> 3;
-    const int tile_first = bands ? (int)(blockIdx.x & 7) * band_len + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int gstep = bands ? (int)(gridDim.x >> 3) : (int)gridDim.x;
-    const int n_tiles = bands ? min(n_tiles_all, ((int)(blockIdx.x & 7) + 1) * band_len) : n_tiles_all;   // end of this workgroup's range
+    // which tiles this workgroup walks: plain or in XCD bands (tilewalk.h)
+    const TileWalk walk = tile_walk(blockIdx.x, gridDim.x, n_tiles_all, bands);
+    const int tile_first = walk.first, gstep = walk.step, n_tiles = walk.end;
     constexpr bool CAN_STATS = G::ACC * NT <= 4 || FWD;  // register budget of the consumer waves
     const bool fuse_stats = !PS && !ACT && CAN_STATS && (a.stat_partials != nullptr || a.stat_acc != nullptr);   // forward: bn statistics of the output
     const bool fuse_bnred = !FWD && (PS || CAN_STATS) && (a.bnred_partials != nullptr || a.bnred_acc != nullptr);  // backward-data: dgamma / dbeta sums of the layer `out` belongs to
@@ -1415,12 +1410,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a, int tile
             unsigned pok;
         };
         Fetched R0;
-        // the fetch cursor runs ahead of the commits.  Its tile coordinates advance incrementally (no division per item)
+        // the fetch cursor runs ahead of the commits.  Its tile coordinates advance incrementally (TileCursor: no division per item)
         // and the chunk offsets / validity bits of its tile are computed once per tile, not once per (tile, slab) item.
-        const int per_img = tiles_x * tiles_y;
-        const int step_x = gstep % tiles_x, step_y = (gstep / tiles_x) % tiles_y, step_n = gstep / per_img;
-        int ftile = tile_first, fslab = 0;
-        int ftx = ftile % tiles_x, fty = (ftile / tiles_x) % tiles_y, fn = ftile / per_img;
+        TileCursor fcur(tile_first, gstep, tiles_x, tiles_y);
+        int fslab = 0;
         // Round 4, "VALU diet" (tools/micro/simd_sharing.hip: on a SIMD, MFMAs and the VALU instructions of EVERY wave share one issue port —
         // a conv item's time is the sum of its MFMA cycles and 4 x the VALU instructions of both roles): the patch and filter fetches are
         // BUFFER loads — address = per-image descriptor (SGPRs) + a 32-bit byte offset computed once per tile (VGPR) + the slab's offset
@@ -1431,7 +1424,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a, int tile
         int foff[NP];   // byte offset within the image (0xFFFFF000 = padding)
         unsigned fpok = 0;
         auto enter_tile = [&]() __attribute__((always_inline)) {
-            const int x0 = G::in_x0(ftx), y0 = G::in_y0(fty);
+            const int x0 = G::in_x0(fcur.pos.tx), y0 = G::in_y0(fcur.pos.ty);
             fpok = 0;
     #pragma unroll
             for (int jj = 0; jj < NP; ++jj) {
@@ -1442,8 +1435,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a, int tile
             }
         };
         auto fetch = [&](Fetched& R) __attribute__((always_inline)) {
-            const bf16* pa = xa + (size_t)fn * plane;
-            const bf16* pb = (KIND == SRC_ACT2 || KIND == SRC_SUM2) ? xb + (size_t)fn * plane : nullptr;
+            const bf16* pa = xa + (size_t)fcur.pos.n * plane;
+            const bf16* pb = (KIND == SRC_ACT2 || KIND == SRC_SUM2) ? xb + (size_t)fcur.pos.n * plane : nullptr;
             const int cc = fslab * 32;
             R.pok = fpok;
             const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(pa), 0, plane_bytes, 0x00020000);
@@ -1461,11 +1454,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a, int tile
                 }
             }
             if (++fslab == n_slabs) {   // cursor -> the workgroup's next tile
-                fslab = 0; ftile += gstep;
-                ftx += step_x; if (ftx >= tiles_x) { ftx -= tiles_x; ++fty; }
-                fty += step_y; if (fty >= tiles_y) { fty -= tiles_y; ++fn; }
-                fn += step_n;
-                if (ftile < n_tiles) enter_tile();
+                fslab = 0;
+                fcur.advance();
+                if (fcur.tile < n_tiles) enter_tile();
             }
         };
         const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(wsrc), 0, 9 * a.c_out * c_red * 2, 0x00020000);
@@ -1500,7 +1491,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a, int tile
                     if ((tid >> 2) + 64 * j < 9 * C_OUT) *reinterpret_cast<u32x4*>(wbuf + wdst[j]) = wraw[j];
             }
         };
-        if (ftile < n_tiles) { enter_tile(); fetch(R0); if (!wres) fetch_w(0); }
+        if (fcur.tile < n_tiles) { enter_tile(); fetch(R0); if (!wres) fetch_w(0); }
         if (wres && tile < n_tiles) {   // resident form: every filter slab goes to its own LDS block once
             for (int sl = 0; sl < n_slabs; ++sl) {
                 fetch_w(sl);
@@ -1524,13 +1515,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a, int tile
         const bf16* ylayer = reinterpret_cast<const bf16*>(a.bnred_y);
         unsigned epix[PST ? ECH : 1];
         auto estat_begin = [&](int et, u32x4 (&yv)[ECH], unsigned& evalid) __attribute__((always_inline)) {   // the y operands are requested ...
-            const int tx = et % tiles_x, ty = (et / tiles_x) % tiles_y, n = et / per_img;
+            const TilePos t = tile_pos(et, tiles_x, tiles_y);
             evalid = 0;
 #pragma unroll
             for (int j = 0; j < ECH; ++j) {
                 const int q = eq0 + EQ_STEP * j;
                 size_t pix; bool valid;
-                G::out_pixel(q >> 7, a, n, ty, tx, (q >> 5) & 3, q & 31, pix, valid);
+                G::out_pixel(q >> 7, a, t.n, t.ty, t.tx, (q >> 5) & 3, q & 31, pix, valid);
                 if (PS != 4) yv[j] = *reinterpret_cast<const u32x4*>(ylayer + pix * a.c_out + co_base + ek * 8);
                 if constexpr (PST) epix[j] = (unsigned)pix;   // (< 2^31 elements per tensor: host check) where this chunk's pixel is stored
                 evalid |= (valid ? 1u : 0u) << j;
@@ -1571,7 +1562,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a, int tile
 #endif
             TOCK(t_a);
             TICK();
-            if (ftile < n_tiles) fetch(R);
+            if (fcur.tile < n_tiles) fetch(R);
             if (!wres && n_slabs > 1 && (slab + 1 < n_slabs || tile + gstep < n_tiles)) fetch_w(slab + 1 < n_slabs ? slab + 1 : 0);
             if constexpr (PS != 0) { if ((ps || pst) && et >= 0) estat_end(eit, eyv, evalid); }
             TOCK(t_b);
@@ -1627,14 +1618,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a, int tile
         const bool rmw_any = !FWD && G::RMW_PREFETCH && a.out_accumulate;
         const bool cons_bnred = fuse_bnred && PS != 1 && PS != 5;   // the consumers keep the bn backward sums (and fetch y for them)
         const bool pre_any = rmw_any || cons_bnred;
-        auto prefetch_epilogue = [&](int t, auto& o, auto& y, bool want_old, bool want_y) __attribute__((always_inline)) {
-            const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, n = t / (tiles_x * tiles_y);
+        auto prefetch_epilogue = [&](int tile_, auto& o, auto& y, bool want_old, bool want_y) __attribute__((always_inline)) {
+            const TilePos t = tile_pos(tile_, tiles_x, tiles_y);
             const bf16* out = reinterpret_cast<const bf16*>(a.out);
             const bf16* yl = reinterpret_cast<const bf16*>(a.bnred_y);
 #pragma unroll
             for (int g = 0; g < G::ACC; ++g) {
                 size_t pix; bool valid;
-                G::out_pixel(g, a, n, ty, tx, wave, col, pix, valid);
+                G::out_pixel(g, a, t.n, t.ty, t.tx, wave, col, pix, valid);
                 const size_t e0 = pix * a.c_out + co_base + 8 * half;
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt)
@@ -1662,16 +1653,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a, int tile
         for (;;) {
             // the epilogue of tile `et`, whose last item was `eit`: right behind its MFMA phase
             auto epilogue = [&](int et, int eit) __attribute__((always_inline)) {
-                const int tx = et % tiles_x, ty = (et / tiles_x) % tiles_y, n = et / (tiles_x * tiles_y);
+                const TilePos t = tile_pos(et, tiles_x, tiles_y);
                 const bool rmw = rmw_any;
 #pragma unroll
                 for (int g = 0; g < G::ACC; ++g) {
                     size_t pix; bool valid;
-                    G::out_pixel(g, a, n, ty, tx, wave, col, pix, valid);
+                    G::out_pixel(g, a, t.n, t.ty, t.tx, wave, col, pix, valid);
 #ifdef ANH_WS_PROFILE
                     if (prof_nostore) valid = false;
 #endif
-                    if constexpr (HEAD) store_pixel_tiles_head(acc[g][0], a, pix, n, valid, half, bnc, C_OUT, hw, hbias);
+                    if constexpr (HEAD) store_pixel_tiles_head(acc[g][0], a, pix, t.n, valid, half, bnc, C_OUT, hw, hbias);
                     else if constexpr (ACT) store_pixel_tiles_act<NT>(acc[g], a, pix, valid, half, co_base, bnc, C_OUT);
                     else {
                         const bool to_ebuf = ps || pst;   // this tile's sums are the producers' / its stores are
@@ -1821,8 +1812,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a, int tile
 #undef TOCK
 }
 
-int ws_target_wgs();
-
 // LDS layout of a persistent conv launch and whether it takes a producer-side form of the fused bn backward sums / stores (PS).
 // with_bnred: the sums are wanted (conv_fused_bnred_blocks asks before ConvArgs::bnred_* are set).
 struct WsLayout { int wres; size_t lds; int ps /* 0, 1 (producer sums), 4 (producer stores), 5 (both) */; int e_off; };
@@ -1862,9 +1851,9 @@ WsLayout ws_layout(const ConvArgs& a, int recs, int acc, int nt, bool with_bnred
 }
 
 template <class G, int NT>
-void launch_ws(const ConvArgs& a, int tiles_x, int tiles_y, int flip, hipStream_t s) {
-    const int n_tiles = tiles_x * tiles_y * a.n, groups = a.c_out / (NT * 32);
-    const dim3 grid((unsigned)std::max(1, std::min(n_tiles, ws_target_wgs() / groups)), (unsigned)groups);
+void launch_ws(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    const int tiles_x = p.tiles_x, tiles_y = p.tiles_y, flip = p.flip;
+    const dim3 grid((unsigned)p.grid_x, (unsigned)p.groups);
     const WsLayout lay = ws_layout(a, G::RECS, G::ACC, NT, a.bnred_partials != nullptr || a.bnred_acc != nullptr);
     const int wres = lay.wres;
     const size_t lds = lay.lds;
@@ -1873,7 +1862,7 @@ void launch_ws(const ConvArgs& a, int tiles_x, int tiles_y, int flip, hipStream_
     const int ps = lay.ps;
     // ANH_WS_XCD_BANDS (1): the workgroups of one XCD walk one contiguous eighth of the tile list (see the kernel); 0 = strided walk
     static const int bands_env = getenv("ANH_WS_XCD_BANDS") ? atoi(getenv("ANH_WS_XCD_BANDS")) : 1;
-    const int bands = bands_env && grid.x % 8 == 0 && grid.x >= 8 ? 1 : 0;
+    const int bands = bands_env && tile_bands_ok(p.grid_x) ? 1 : 0;
     const int flags = wres | (bands << 4) | ((filter_regs_env ? 0 : 1) << 19);   // (bit 6: the profiling build's no-store run)
     auto launch = [&](auto kernel) {
         const dim3 block(512);
@@ -2047,8 +2036,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_stem_mfma_kernel(WgradArgs a, Wg
     const size_t dy_plane = (size_t)a.h_out * a.w_out * 32;
     struct TileAt { int x0, y0, n; };
     auto tile_at = [&](int tile) __attribute__((always_inline)) {
-        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
-        return TileAt{tx * 32, ty * 8, n};
+        const TilePos t = tile_pos(tile, tiles_x, tiles_y);
+        return TileAt{t.tx * 32, t.ty * 8, t.n};
     };
     auto fetch_img = [&](Regs& R, const TileAt& t) __attribute__((always_inline)) {
         if (!img_thread) return;
@@ -2156,13 +2145,12 @@ bool stem_wgrad_mfma_ok(const WgradArgs& a) {
            (int64_t)a.src.img_h * a.src.img_w * a.c_in < 0x7FFFFFF0ll;   // (one image behind a buffer descriptor, 32-bit byte offsets)
 }
 int stem_wgrad_mfma_blocks(const WgradArgs& a) {
-    const int tiles = ((a.w_out + 31) / 32) * ((a.h_out + 7) / 8) * a.n;
     static const int target = getenv("ANH_STEM_WGRAD_BLOCKS") ? atoi(getenv("ANH_STEM_WGRAD_BLOCKS")) : 512;
-    return std::max(1, std::min(tiles, target));
+    return std::max(1, std::min(tiles_stem(a.h_out, a.w_out, a.n).total, target));
 }
 void launch_wgrad_stem_mfma(const WgradArgs& a, hipStream_t s) {
-    const int tiles_x = (a.w_out + 31) / 32, tiles_y = (a.h_out + 7) / 8;
-    const int total = tiles_x * tiles_y * a.n, blocks = stem_wgrad_mfma_blocks(a);
+    const TileCounts t = tiles_stem(a.h_out, a.w_out, a.n);
+    const int tiles_x = t.tiles_x, tiles_y = t.tiles_y, total = t.total, blocks = stem_wgrad_mfma_blocks(a);
     const WgSide dy{reinterpret_cast<const bf16*>(a.dy), nullptr, nullptr, nullptr, nullptr, nullptr, a.h_out, a.w_out, 32};
     const size_t lds = 2 * (256 * 64 + (size_t)(a.c_in + 1) * (12 * 5 * 64 + 64));  // two buffers, each with its zero plane
     if (a.dy_y) {
@@ -2191,9 +2179,8 @@ WgPlan wgrad_plan_mfma(const WgradArgs& a) {
     p.ntc = ntc_;
     p.zgroups = c_tile / (p.ntc * 32);   // 256 tile channels: two groups of 128 (warp-specialised kernel only)
     p.slabs = c_patch / 32;
-    p.tiles_x = (lr_w + 31) / 32;
-    p.tiles_y = (lr_h + th - 1) / th;
-    p.total = p.tiles_x * p.tiles_y * a.n;
+    const TileCounts t = tiles_wgrad(lr_h, lr_w, th, a.n);
+    p.tiles_x = t.tiles_x; p.tiles_y = t.tiles_y; p.total = t.total;
     p.lds = (size_t)(a.stride == 1 ? (th + 2) * 34 : 594) * 64 + (size_t)p.ntc * th * 32 * 64;
     const size_t tab = (size_t)p.ntc * 32 * 16;            // the tile side's bn constants
     if (p.ws) p.lds = 2 * p.lds + tab;                     // the warp-specialised kernel always runs two buffers
@@ -2212,7 +2199,7 @@ void launch_wg(const WgParams& prm, const WgPlan& p, hipStream_t s) {
             ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), p.lds);
             // MEASURED (13 same-box rounds in two calls): 1.7314 -> 1.7217 and 1.7026 -> 1.6960 ms per step (-0.4 ... -0.6 %).  Default 1.
             static const int wbands_env = getenv("ANH_WGRAD_XCD_BANDS") ? atoi(getenv("ANH_WGRAD_XCD_BANDS")) : 1;
-            const int wbands = wbands_env && p.splits % 8 == 0 && p.splits >= 8 ? 1 : 0;
+            const int wbands = wbands_env && tile_bands_ok(p.splits) ? 1 : 0;
             hipLaunchKernelGGL(kernel, dim3(p.splits, p.slabs, p.zgroups), dim3(512), p.lds, s, prm, p.tiles_x, p.tiles_y, p.total, p.splits | (wbands << 30));
         };
         constexpr bool can_be_cont = STRIDE == 2 && KP == SRC_RAW;   // cont: the patch is dy (raw), its channels are the output channels
@@ -2284,8 +2271,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_down_mfma_kernel(ConvArgs a, W
     char* lds_w = smem + RECS * 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
     const int tile = blockIdx.x;
-    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
-    const int x0 = tx * 32, y0 = ty * DTH;
+    const TilePos t = tile_pos(tile, tiles_x, tiles_y);
+    const int x0 = t.tx * 32, y0 = t.ty * DTH, n = t.n;
     const int co_base = blockIdx.y * C_OUT;
     const bf16* wsrc = reinterpret_cast<const bf16*>(a.w_bf16);
 
@@ -2341,8 +2328,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_up_mfma_kernel(ConvArgs a, WgS
     char* lds_w = smem + RECS * 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
     const int tile = blockIdx.x;
-    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
-    const int j0 = tx * 32, i0 = ty * UTH;  // low-res positions; output pixel = (2i + py, 2j + px)
+    const TilePos t = tile_pos(tile, tiles_x, tiles_y);
+    const int j0 = t.tx * 32, i0 = t.ty * UTH, n = t.n;  // low-res positions; output pixel = (2i + py, 2j + px)
     const bf16* wsrc = reinterpret_cast<const bf16*>(a.w_bf16);
 
     f32x16 acc[4][NT];
@@ -2459,8 +2446,8 @@ __global__ __launch_bounds__(256, (ACT ? 4 : 2)) void stem_mfma_kernel(ConvArgs 
     for (int u = 0; u < NPX; ++u) { const int i = min(tid + 256 * u, 12 * 36 - 1); ppy[u] = i / 36; ppx[u] = i - ppy[u] * 36; }
     const size_t img_pixels = (size_t)a.src.img_h * a.src.img_w;
     auto fetch = [&](int tile_) __attribute__((always_inline)) {
-        const int tx = tile_ % tiles_x, ty = (tile_ / tiles_x) % tiles_y, n = tile_ / (tiles_x * tiles_y);
-        const int x0 = tx * 32, y0 = ty * 8;
+        const TilePos t = tile_pos(tile_, tiles_x, tiles_y);
+        const int x0 = t.tx * 32, y0 = t.ty * 8, n = t.n;
         const uint8_t* img = a.src.img + (size_t)a.src.image_of(n) * a.src.img_sample_stride;
         pvalid = 0;
 #pragma unroll
@@ -2485,8 +2472,8 @@ __global__ __launch_bounds__(256, (ACT ? 4 : 2)) void stem_mfma_kernel(ConvArgs 
     int tile = blockIdx.x;
     if (tile < total_tiles) fetch(tile);
     for (; tile < total_tiles; tile += gridDim.x) {
-        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
-        const int x0 = tx * 32, y0 = ty * 8;
+        const TilePos t = tile_pos(tile, tiles_x, tiles_y);
+        const int x0 = t.tx * 32, y0 = t.ty * 8, n = t.n;
         __syncthreads();
 #pragma unroll
         for (int u = 0; u < NPX; ++u) {
@@ -2562,14 +2549,13 @@ bool stem_mfma_ok(const ConvArgs& a) {
            a.h_in == a.h_out && a.w_in == a.w_out && !a.bias && !a.out_nchw && a.out_dtype == DT_BF16 && a.w_f32;
 }
 int stem_mfma_blocks(const ConvArgs& a) {
-    const int total = ((a.w_out + 31) / 32) * ((a.h_out + 7) / 8) * a.n;
     static const int env = getenv("ANH_STEM_BLOCKS") ? atoi(getenv("ANH_STEM_BLOCKS")) : 0;
     // ONE round of resident workgroups: four per CU for the inference form, three for the training form (152 VGPRs)
-    return std::min(total, env > 0 ? env : a.out_scale ? 1024 : 768);
+    return std::min(tiles_stem(a.h_out, a.w_out, a.n).total, env > 0 ? env : a.out_scale ? 1024 : 768);
 }
 void launch_stem_mfma(const ConvArgs& a, hipStream_t s) {
-    const int tiles_x = (a.w_out + 31) / 32, tiles_y = (a.h_out + 7) / 8;
-    const int total = tiles_x * tiles_y * a.n;
+    const TileCounts t = tiles_stem(a.h_out, a.w_out, a.n);
+    const int tiles_x = t.tiles_x, tiles_y = t.tiles_y, total = t.total;
     const dim3 grid((unsigned)stem_mfma_blocks(a)), block(256);
     ANH_REQUIRE(!a.out_scale || (a.out_shift == a.out_scale + 32 && !a.stat_partials), "stem_mfma: the activation-storing form takes [scale | shift] as one table");
     if (a.out_scale) {
@@ -2583,8 +2569,8 @@ void launch_stem_mfma(const ConvArgs& a, hipStream_t s) {
 
 
 template <int NT, int TAPS>
-void launch_down(const ConvArgs& a, hipStream_t s) {
-    const int tiles_x = (a.w_out + 31) / 32, tiles_y = (a.h_out + 3) / 4;
+void launch_down(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    const int tiles_x = p.tiles_x, tiles_y = p.tiles_y;
     const dim3 grid((unsigned)(tiles_x * tiles_y * a.n), (unsigned)(a.c_out / (NT * 32))), block(256);
     const size_t lds = (size_t)9 * 66 * 64 + (size_t)TAPS * NT * 32 * 64;
     const WgSide src = side_of(a);
@@ -2597,8 +2583,8 @@ void launch_down(const ConvArgs& a, hipStream_t s) {
 }
 
 template <int NT>
-void launch_up(const ConvArgs& a, hipStream_t s) {
-    const int tiles_x = (a.w_in + 1 + 31) / 32, tiles_y = (a.h_in + 1 + 3) / 4;
+void launch_up(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    const int tiles_x = p.tiles_x, tiles_y = p.tiles_y;
     const dim3 grid((unsigned)(tiles_x * tiles_y * a.n)), block(256);
     const size_t lds = (size_t)5 * 33 * 64 + (size_t)9 * NT * 32 * 64;
     const WgSide src = side_of(a);
@@ -2632,9 +2618,6 @@ bool mfma_conv_supported(const ConvArgs& a) {
 }
 
 namespace {
-// which kernel a supported 3x3 layer takes, and its launch geometry
-struct ConvPlan { int geo /*0 s1, 1 down, 2 up*/, nt, tiles_x, tiles_y, flip, form /*0 classic one-tile kernels, 2 warp-specialised*/, grid_x, groups; };
-
 int ws_target_wgs() { static const int t = getenv("ANH_WS_WGS") ? atoi(getenv("ANH_WS_WGS")) : 256; return t; }  // 1 per CU
 
 ConvPlan conv_plan(const ConvArgs& a) {
@@ -2646,14 +2629,12 @@ ConvPlan conv_plan(const ConvArgs& a) {
     p.geo = a.stride == 1 ? 0 : (a.gather == 0 ? 1 : 2);
     p.nt = a.c_out == 32 ? 1 : 2;  // 64, or 128 as two workgroup groups of 64 output channels
     p.flip = p.geo == 0 ? a.gather : 0;
-    if (p.geo == 0) { p.tiles_x = (a.w_out + TW - 1) / TW; p.tiles_y = (a.h_out + TH - 1) / TH; }
-    else if (p.geo == 1) { p.tiles_x = (a.w_out + 31) / 32; p.tiles_y = (a.h_out + 3) / 4; }
-    else { p.tiles_x = (a.w_in + 1 + 31) / 32; p.tiles_y = (a.h_in + 1 + 3) / 4; }
+    const TileCounts t = p.geo == 0 ? tiles_s1(a.h_out, a.w_out, a.n) : p.geo == 1 ? tiles_down(a.h_out, a.w_out, a.n) : tiles_up(a.h_in, a.w_in, a.n);
+    p.tiles_x = t.tiles_x; p.tiles_y = t.tiles_y;
     const int bit = 1 << p.geo;
     p.form = (small_plane && (wsm & bit)) ? 2 : 0;
     p.groups = a.c_out / (p.nt * 32);
-    const int n_tiles = p.tiles_x * p.tiles_y * a.n;
-    p.grid_x = std::max(1, std::min(n_tiles, ws_target_wgs() / p.groups));
+    p.grid_x = std::max(1, std::min(t.total, ws_target_wgs() / p.groups));
     return p;
 }
 }  // namespace
@@ -2720,21 +2701,18 @@ void launch_conv_mfma(const ConvArgs& a, hipStream_t s) {
     ANH_REQUIRE(!a.src.a_tab.acc || conv_folds_bn_tables(a), "conv_mfma: this layer's kernel does not fold bn accumulator tables");
     ANH_REQUIRE(!a.bnred_partials || (conv_fused_bnred_blocks(a) > 0 && !a.stat_partials), "conv_mfma: this layer's kernel does not fuse the bn backward reduction");
     if (p.geo == 0) {
-        if (p.form == 2) {
-            if (p.nt == 1) launch_ws<GeoS1, 1>(a, p.tiles_x, p.tiles_y, p.flip, s);
-            else launch_ws<GeoS1, 2>(a, p.tiles_x, p.tiles_y, p.flip, s);
-        }
-        else if (a.c_out == 32) launch_s1<1, 9>(a, s);
-        else launch_s1<2, 9>(a, s);
+        if (p.form == 2) { if (p.nt == 1) launch_ws<GeoS1, 1>(a, p, s); else launch_ws<GeoS1, 2>(a, p, s); }
+        else if (a.c_out == 32) launch_s1<1, 9>(a, p, s);
+        else launch_s1<2, 9>(a, p, s);
     } else if (p.geo == 1) {
-        if (p.form == 2) { if (p.nt == 1) launch_ws<GeoDown, 1>(a, p.tiles_x, p.tiles_y, 0, s); else launch_ws<GeoDown, 2>(a, p.tiles_x, p.tiles_y, 0, s); }
-        else if (a.c_out == 32) launch_down<1, 9>(a, s);
-        else if (a.c_out == 128) launch_down<4, 3>(a, s);
-        else launch_down<2, 9>(a, s);   // 64, or 256 as four groups of 64
+        if (p.form == 2) { if (p.nt == 1) launch_ws<GeoDown, 1>(a, p, s); else launch_ws<GeoDown, 2>(a, p, s); }
+        else if (a.c_out == 32) launch_down<1, 9>(a, p, s);
+        else if (a.c_out == 128) launch_down<4, 3>(a, p, s);
+        else launch_down<2, 9>(a, p, s);   // 64, or 256 as four groups of 64
     } else {
-        if (p.form == 2) { if (p.nt == 1) launch_ws<GeoUp, 1>(a, p.tiles_x, p.tiles_y, 0, s); else launch_ws<GeoUp, 2>(a, p.tiles_x, p.tiles_y, 0, s); }
-        else if (a.c_out == 32) launch_up<1>(a, s);
-        else launch_up<2>(a, s);
+        if (p.form == 2) { if (p.nt == 1) launch_ws<GeoUp, 1>(a, p, s); else launch_ws<GeoUp, 2>(a, p, s); }
+        else if (a.c_out == 32) launch_up<1>(a, p, s);
+        else launch_up<2>(a, p, s);
     }
 }
 
