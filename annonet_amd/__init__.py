@@ -7,6 +7,7 @@ is the thin host-side mirror used by tests and bench.py.  There is no CPU fallba
 from ._lib import ANH_BF16, ANH_FP32, LABEL_IGNORE, AnnonetHipError, build, lib  # noqa: F401
 from .netpimpl import (Dataset, RuntimeNet, TrainingNet, REGION_DTYPE, argmax_device, annonet_infer, annonet_infer_device, annonet_infer_regions, label_blobs, regions, regions_device, detection_filter, detection_filter_device, label_blobs_batch, regions_batch, regions_batch_device, annonet_infer_regions_batch, annonet_infer_regions_scaled, annonet_infer_regions_scaled_batch, annonet_infer_scaled, annonet_infer_scaled_device, annonet_infer_scaled_batch, annonet_infer_scaled_batch_device, annonet_infer_batch, annonet_infer_batch_device, infer_batch_plan, labels_from_logits_device, count_steps_without_decrease, dnn_envelope_pack, dnn_envelope_unpack,  # noqa: F401
                        ignore_large_nonzero_regions, score, score_batch, score_device, score_batch_device,
+                       EVAL_DTYPE, EvalResult, eval_logits_device,
                        net_config, net_layers,
                        op_conv_backward_data, op_conv_backward_data_bn, op_conv_backward_filter, op_conv_backward_filter_bn,
                        op_conv_forward, op_conv_forward_stats, outpaint,

@@ -105,6 +105,10 @@ class Region(C.Structure):   # anh_region
                [("area", C.c_int64), ("seeds", C.c_int64), ("peak", C.c_float)]
 
 
+class EvalImage(C.Structure):   # anh_eval_image
+    _fields_ = [("loss_sum", C.c_double), ("weight_sum", C.c_double), ("counted", C.c_uint64), ("unclassified", C.c_uint64)]
+
+
 class TilingParams(C.Structure):
     _fields_ = [("max_tile_width", C.c_int), ("max_tile_height", C.c_int), ("overlap_x", C.c_int), ("overlap_y", C.c_int)]
 
@@ -156,6 +160,11 @@ _SIGNATURES = {  # ConvDesc / OpInput are defined above
     "anh_score_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "anh_score_batch": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "anh_score": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "anh_eval_logits_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "anh_runtime_evaluate_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "anh_runtime_evaluate": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "anh_trainer_evaluate": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "anh_trainer_evaluate_device": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "anh_infer_device": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(TilingParams), C.POINTER(Tile), C.c_size_t, _P, _P]),
     "anh_infer_batch": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(TilingParams), C.POINTER(_P), C.POINTER(_P)]),
     "anh_infer_batch_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(TilingParams), _P, _P]),

@@ -210,6 +210,9 @@ struct anh_trainer {
     // own staging sets; StartTraining splits the mini-batch along N, one all-reduce (RCCL) sums the flat gradient buckets, every
     // replica applies the identical update.  Batch-norm statistics are per replica.  The last member: the engines
     // drain and die before the staging sets, the loss ring and the events above are released.
+    // eval_net: the inference net of anh_trainer_evaluate, made on first use (one replica on the first device, like a snapshot) and
+    // refreshed from the parameters on every call; it shares nothing with the training engines.
+    std::unique_ptr<anh_runtime> eval_net;
     ReplicaSet reps;
 };
 
@@ -1030,6 +1033,90 @@ int anh_score(anh_runtime* h, const uint16_t* truth, const uint16_t* result, int
     return anh_score_batch(h, &truth, &result, 1, classes, height, width, per_pixel, per_region, labelled);
 }
 
+// ---- held-out evaluation (Engine::evaluate_logits, Engine::evaluate_device) ----
+namespace {
+void require_eval_sizes(int n, int height, int width) {
+    ANH_REQUIRE(n >= 1, "evaluate: the batch needs at least one image");
+    ANH_REQUIRE(height >= 1 && width >= 1, "evaluate: empty window");
+    if (anh_device_count() == 0) fail(ANH_ERR_DEVICE, "no MI355X / HIP device visible");   // no evaluation without a GPU, whatever else is passed
+}
+// host samples -> the engine's staging buffers [images | labels u16 | weights f32], then the device form; the predicted maps come back
+// after the call's one wait
+void run_host_evaluate(anh_runtime* h, const uint8_t* const* images, const anh_wlabel* const* labels, int n, int height, int width, const double* gains,
+                       anh_eval_image* per_image, uint64_t* confusion, uint16_t* predicted) {
+    DeviceScope scope(h->reps.device_of(0));
+    Engine& e = h->reps.engine(0);
+    const size_t plane = (size_t)height * width, C = (size_t)e.spec.cfg.in_channels;
+    e.stage_image.reserve((size_t)n * plane * C);
+    e.stage_labels.reserve((size_t)n * plane * sizeof(uint16_t));
+    e.stage_weights.reserve((size_t)n * plane * sizeof(float));
+    if (predicted) e.stage_result.reserve((size_t)n * plane * sizeof(uint16_t));
+    std::vector<uint16_t> lab((size_t)n * plane);
+    std::vector<float> wgt((size_t)n * plane);
+    for (int i = 0; i < n; ++i) {
+        const anh_wlabel* src = labels[i];
+        uint16_t* dl = lab.data() + (size_t)i * plane;
+        float* dw = wgt.data() + (size_t)i * plane;
+        for (size_t p = 0; p < plane; ++p) { dl[p] = src[p].label; dw[p] = src[p].weight; }
+        HIP_CHECK(hipMemcpyAsync(e.stage_image.as<uint8_t>() + (size_t)i * plane * C, images[i], plane * C, hipMemcpyHostToDevice, e.stream));
+    }
+    HIP_CHECK(hipMemcpyAsync(e.stage_labels.p, lab.data(), lab.size() * sizeof(uint16_t), hipMemcpyHostToDevice, e.stream));
+    HIP_CHECK(hipMemcpyAsync(e.stage_weights.p, wgt.data(), wgt.size() * sizeof(float), hipMemcpyHostToDevice, e.stream));
+    uint16_t* d_predicted = predicted ? e.stage_result.as<uint16_t>() : nullptr;
+    e.evaluate_device(e.stage_image.as<uint8_t>(), e.stage_labels.as<uint16_t>(), e.stage_weights.as<float>(), n, height, width, gains, per_image, confusion,
+                      d_predicted);
+    if (predicted) HIP_CHECK(hipMemcpy(predicted, d_predicted, (size_t)n * plane * sizeof(uint16_t), hipMemcpyDeviceToHost));   // (the stream is idle)
+}
+// the inference net a trainer keeps for evaluation, with the trainer's parameters as they stand: what anh_trainer_snapshot_runtime
+// builds, kept between calls
+anh_runtime* refreshed_eval_net(anh_trainer* h, int precision) {
+    ANH_REQUIRE(precision == ANH_FP32 || precision == ANH_BF16, "unknown precision");
+    Engine& e = h->engine();
+    std::vector<float> p((size_t)e.spec.n_params), r((size_t)e.spec.n_running);
+    e.get_params(p.data(), r.data());   // synchronises: a step in flight finishes first
+    if (!h->eval_net || h->eval_net->reps.engine(0).spec.cfg.precision != precision) {
+        anh_net_config cfg = e.spec.cfg;
+        cfg.precision = precision;
+        auto rt = std::make_unique<anh_runtime>();
+        rt->build(cfg, h->reps.size() > 1 ? h->reps.device_of(0) : -1);
+        h->eval_net = std::move(rt);
+    }
+    h->eval_net->set_params_all(p.data(), r.data());
+    return h->eval_net.get();
+}
+}  // namespace
+
+int anh_eval_logits_device(anh_runtime* h, const float* d_logits, const uint16_t* d_labels, const float* d_weights, int n, int classes, int height, int width,
+                           const double* gains, anh_eval_image* per_image, uint64_t* confusion, uint16_t* d_predicted) {
+    return guarded([&] {
+        require_eval_sizes(n, height, width);
+        ANH_REQUIRE(classes >= 1 && classes <= kEvalMaxClasses, "evaluate: the class count must be within 1..64");
+        ANH_REQUIRE(h && d_logits && d_labels && per_image, "null argument");
+        DeviceScope scope(h->reps.device_of(0));
+        h->reps.engine(0).evaluate_logits(d_logits, d_labels, d_weights, n, classes, height, width, gains, per_image, confusion, d_predicted);
+    });
+}
+
+int anh_runtime_evaluate_device(anh_runtime* h, const uint8_t* d_images, const uint16_t* d_labels, const float* d_weights, int n, int height, int width,
+                                const double* gains, anh_eval_image* per_image, uint64_t* confusion, uint16_t* d_predicted) {
+    return guarded([&] {
+        require_eval_sizes(n, height, width);
+        ANH_REQUIRE(h && d_images && d_labels && per_image, "null argument");
+        DeviceScope scope(h->reps.device_of(0));
+        h->reps.engine(0).evaluate_device(d_images, d_labels, d_weights, n, height, width, gains, per_image, confusion, d_predicted);
+    });
+}
+
+int anh_runtime_evaluate(anh_runtime* h, const uint8_t* const* images, const anh_wlabel* const* labels, int n, int height, int width, const double* gains,
+                         anh_eval_image* per_image, uint64_t* confusion, uint16_t* predicted) {
+    return guarded([&] {
+        require_eval_sizes(n, height, width);
+        ANH_REQUIRE(h && images && labels && per_image, "null argument");
+        for (int i = 0; i < n; ++i) ANH_REQUIRE(images[i] && labels[i], "evaluate: null sample");
+        run_host_evaluate(h, images, labels, n, height, width, gains, per_image, confusion, predicted);
+    });
+}
+
 // ---- annonet_infer() over several images of one size (Engine::infer_batch_device) ----
 int anh_infer_batch_device(anh_runtime* h, const uint8_t* d_images, int n, int height, int width, const double* gains, const anh_tiling_params* tiling,
                            uint16_t* d_results, float* d_blended) {
@@ -1607,6 +1694,27 @@ int anh_trainer_snapshot_runtime(anh_trainer* h, int precision, anh_runtime** ou
         rt->build(cfg, h->reps.size() > 1 ? h->reps.device_of(0) : -1);
         rt->set_params_all(p.data(), r.data());
         *out = rt.release();
+    });
+}
+
+int anh_trainer_evaluate(anh_trainer* h, int precision, const uint8_t* const* images, const anh_wlabel* const* labels, int n, int height, int width,
+                         const double* gains, anh_eval_image* per_image, uint64_t* confusion, uint16_t* predicted) {
+    return guarded([&] {
+        require_eval_sizes(n, height, width);
+        ANH_REQUIRE(h && images && labels && per_image, "null argument");
+        for (int i = 0; i < n; ++i) ANH_REQUIRE(images[i] && labels[i], "evaluate: null sample");
+        run_host_evaluate(refreshed_eval_net(h, precision), images, labels, n, height, width, gains, per_image, confusion, predicted);
+    });
+}
+
+int anh_trainer_evaluate_device(anh_trainer* h, int precision, const uint8_t* d_images, const uint16_t* d_labels, const float* d_weights, int n, int height,
+                                int width, const double* gains, anh_eval_image* per_image, uint64_t* confusion, uint16_t* d_predicted) {
+    return guarded([&] {
+        require_eval_sizes(n, height, width);
+        ANH_REQUIRE(h && d_images && d_labels && per_image, "null argument");
+        anh_runtime* rt = refreshed_eval_net(h, precision);
+        DeviceScope scope(rt->reps.device_of(0));
+        rt->reps.engine(0).evaluate_device(d_images, d_labels, d_weights, n, height, width, gains, per_image, confusion, d_predicted);
     });
 }
 

@@ -206,7 +206,26 @@ class Engine {
     // table) and for the matrices.
     void score_stacked(int n, int K, int H, int W, uint64_t* per_pixel, uint64_t* per_region, uint64_t* labelled);
 
+    // ---- held-out evaluation (kernels_eval.hip): loss sums and confusion counts per window ----
+    // The tally on resident logits [n][K][H][W] with labels [n][H][W], weights [n][H][W] (or null = 1) and K gains (host, or null):
+    // per_image [n] and confusion [n][K][K] (or null) on the host, d_predicted [n][H][W] (or null).  A label >= K other than
+    // ANH_LABEL_IGNORE is ANH_ERR_INVALID.  Synchronises once.
+    void evaluate_logits(const float* d_logits, const uint16_t* d_labels, const float* d_weights, int n, int K, int H, int W, const double* gains_host,
+                         anh_eval_image* per_image, uint64_t* confusion, uint16_t* d_predicted);
+    // n windows [n][H][W][C] of the net's own input: forward batches of at most tile_batch(H, W) windows, each followed by the tally on its
+    // logits.  The logits and layer tensors of the largest batch, the partials, the outputs and the error flag are reserved before the
+    // first kernel.  Synchronises once.
+    void evaluate_device(const uint8_t* d_images, const uint16_t* d_labels, const float* d_weights, int n, int H, int W, const double* gains_host,
+                         anh_eval_image* per_image, uint64_t* confusion, uint16_t* d_predicted);
+    DevBuf eval_partials, eval_out;
+    std::vector<uint64_t> host_eval;   // eval_out as it comes back: [n images | n K K cells | error flag]
+
   private:
+    void reserve_eval(int n, int batch, int K, int H, int W);
+    void eval_begin(int n, int K);
+    void eval_batch(const float* d_logits, const uint16_t* d_labels, const float* d_weights, int first, int count, int K, int H, int W, const double* d_gains,
+                    uint16_t* d_predicted);
+    void eval_finish(int n, int K, anh_eval_image* per_image, uint64_t* confusion);
     void plan_dims(int n, int h, int w);
     void plan_dims_unguarded(int n, int h, int w);
     // Table mode (bnacc.h, default in bf16 training when every layer's kernels support it; ANH_BN_TABLES=0 switches it off): the bn

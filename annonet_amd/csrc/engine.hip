@@ -1354,4 +1354,79 @@ void Engine::score_stacked(int n, int K, int H, int W, uint64_t* per_pixel, uint
     if (per_region) std::copy(host_score.begin() + n + (ptrdiff_t)cells, host_score.end(), per_region);
 }
 
+// ---- held-out evaluation: eval_out = [n anh_eval_image | n K K cells | error flag] ----
+static_assert(sizeof(anh_eval_image) == 4 * sizeof(uint64_t), "anh_eval_image is four 8-byte words");
+
+void Engine::reserve_eval(int n, int batch, int K, int H, int W) {
+    ANH_REQUIRE(n >= 1 && batch >= 1, "evaluate: the batch needs at least one image");
+    ANH_REQUIRE(K >= 1 && K <= kEvalMaxClasses, "evaluate: the class count must be within 1..64");
+    ANH_REQUIRE(H >= 1 && W >= 1, "evaluate: empty window");
+    const size_t words = (size_t)n * 4 + (size_t)n * K * K + 1;
+    eval_partials.reserve(eval_partial_doubles(batch, (int64_t)H * W) * sizeof(double));
+    eval_out.reserve(words * sizeof(uint64_t));
+    host_eval.resize(words);
+}
+
+void Engine::eval_begin(int n, int K) {
+    HIP_CHECK(hipMemsetAsync(eval_out.p, 0, ((size_t)n * 4 + (size_t)n * K * K + 1) * sizeof(uint64_t), stream));
+}
+
+// the tally of images [first, first + count) of the call; the pointers are those of the batch's first image
+void Engine::eval_batch(const float* d_logits, const uint16_t* d_labels, const float* d_weights, int first, int count, int K, int H, int W, const double* d_gains,
+                        uint16_t* d_predicted) {
+    const size_t n_all = (host_eval.size() - 1) / (4 + (size_t)K * K);
+    anh_eval_image* images = eval_out.as<anh_eval_image>();
+    unsigned long long* cells = eval_out.as<unsigned long long>() + n_all * 4;
+    int* flag = reinterpret_cast<int*>(cells + n_all * K * K);
+    const double px = (double)count * H * W;
+    const int tok = prof.begin(stream, "eval_tally", 0, px * (K * 4.0 + 2.0 + (d_weights ? 4.0 : 0.0) + (d_predicted ? 2.0 : 0.0)));
+    launch_eval_tally(d_logits, d_labels, d_weights, count, K, (int64_t)H * W, d_gains, images + first, cells + (size_t)first * K * K, d_predicted,
+                      eval_partials.as<double>(), flag, stream);
+    prof.end(stream, tok);
+}
+
+void Engine::eval_finish(int n, int K, anh_eval_image* per_image, uint64_t* confusion) {
+    const size_t cells = (size_t)n * K * K;
+    HIP_CHECK(hipMemcpyAsync(host_eval.data(), eval_out.p, host_eval.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    wait_stream(stream, bounded_waits);   // the call's one wait
+    if (host_eval.back() != 0) fail(ANH_ERR_INVALID, "evaluate: a label value exceeds the class count");
+    if (per_image) std::memcpy(per_image, host_eval.data(), (size_t)n * sizeof(anh_eval_image));
+    if (confusion) std::copy(host_eval.begin() + (ptrdiff_t)n * 4, host_eval.begin() + (ptrdiff_t)n * 4 + (ptrdiff_t)cells, confusion);
+}
+
+void Engine::evaluate_logits(const float* d_logits, const uint16_t* d_labels, const float* d_weights, int n, int K, int H, int W, const double* gains_host,
+                             anh_eval_image* per_image, uint64_t* confusion, uint16_t* d_predicted) {
+    ANH_REQUIRE(d_logits && d_labels, "evaluate: null argument");
+    reserve_eval(n, n, K, H, W);
+    const double* d_gains = upload_gains(gains_host, K);
+    eval_begin(n, K);
+    eval_batch(d_logits, d_labels, d_weights, 0, n, K, H, W, d_gains, d_predicted);
+    eval_finish(n, K, per_image, confusion);
+}
+
+void Engine::evaluate_device(const uint8_t* d_images, const uint16_t* d_labels, const float* d_weights, int n, int H, int W, const double* gains_host,
+                             anh_eval_image* per_image, uint64_t* confusion, uint16_t* d_predicted) {
+    ANH_REQUIRE(!training, "evaluate on a training net: use the trainer's evaluate");
+    ANH_REQUIRE(d_images && d_labels, "evaluate: null argument");
+    ANH_REQUIRE(n >= 1 && H >= 1 && W >= 1, "evaluate: empty batch");
+    const int K = spec.cfg.classes, C = spec.cfg.in_channels;
+    const size_t plane = (size_t)H * W;
+    // as few batches as the cap allows, of equal size (infer_device's rule); an image's result does not depend on the cut
+    const int cap = tile_batch(H, W), n_batches = (n + cap - 1) / cap, per = (n + n_batches - 1) / n_batches;
+    // everything before the first kernel: the layer tensors and logits of the largest batch, the partials, the outputs, the gains
+    plan_dims(per, H, W);
+    tile_out.reserve((size_t)per * K * plane * 4);
+    reserve_eval(n, per, K, H, W);
+    if (gains_host) gains_dev.reserve((size_t)K * sizeof(double));
+    const double* d_gains = upload_gains(gains_host);
+    eval_begin(n, K);
+    for (int first = 0; first < n; first += per) {
+        const int count = std::min(per, n - first);
+        forward_inference(image_source(d_images + (size_t)first * plane * C, H, W, C), count, H, W, tile_out.as<float>());
+        eval_batch(tile_out.as<float>(), d_labels + (size_t)first * plane, d_weights ? d_weights + (size_t)first * plane : nullptr, first, count, K, H, W, d_gains,
+                   d_predicted ? d_predicted + (size_t)first * plane : nullptr);
+    }
+    eval_finish(n, K, per_image, confusion);
+}
+
 }  // namespace anh

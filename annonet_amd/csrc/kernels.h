@@ -343,6 +343,17 @@ void launch_score_tally(const uint16_t* d_maps, const uint32_t* d_blobs, int n, 
                         unsigned long long* d_labelled, unsigned long long* d_pixel, hipStream_t s);
 // one thread per vote row: d_region [n][k][k] (cleared by the caller) receives the regions' votes
 void launch_score_decide(const unsigned* d_votes, const unsigned long long* d_row_offsets, int n, int k, uint32_t rows, unsigned long long* d_region, hipStream_t s);
+// ---- held-out evaluation (kernels_eval.hip): loss sums and confusion counts of `count` windows from their logits ----
+// logits [count][k][pixels] fp32, labels [count][pixels] u16, weights [count][pixels] fp32 or null (1 everywhere), gains k doubles or null,
+// predicted [count][pixels] u16 or null; k <= kEvalMaxClasses.  images [count] and confusion [count][k][k] are CLEARED by the caller;
+// partials: eval_partial_doubles(count, pixels) doubles of scratch that need no clearing; *error_flag is set on a label >= k that is not
+// ANH_LABEL_IGNORE.  A workgroup serves kEvalBlockPixels consecutive pixels of ONE image, whatever `count` and the image's index are; the
+// two double sums of an image are the fixed-order sums of its workgroups' partials (eval_finalize, launched behind the tally).
+constexpr int kEvalMaxClasses = 64;       // the net's limit (spec.cpp)
+constexpr int kEvalBlockPixels = 4096;
+size_t eval_partial_doubles(int count, int64_t pixels);
+void launch_eval_tally(const float* d_logits, const uint16_t* d_labels, const float* d_weights, int count, int k, int64_t pixels, const double* d_gains,
+                       anh_eval_image* d_images, unsigned long long* d_confusion, uint16_t* d_predicted, double* d_partials, int* d_error_flag, hipStream_t s);
 void launch_reduce_partials(const float* partials, int splits, int64_t nw, float* out, hipStream_t s);
 
 struct BnFoldJobs;

@@ -13,6 +13,8 @@
 #define ANNONET_HIP_NO_DLIB
 #include "annonet_train_host.h"
 
+#include <hip/hip_runtime_api.h>   // the held-out windows live in HBM: hipMalloc / hipMemcpy / hipFree, nothing else
+
 #include <list>
 #include <map>
 #include <unordered_set>
@@ -34,6 +36,8 @@ struct TrainSettings {
     unsigned loader_threads = std::max(1u, std::thread::hardware_concurrency());
     std::vector<int> devices;
     uint64_t seed = 0;
+    std::string validation_directory, validation_precision;   // held-out images; the precision defaults to the training precision
+    size_t validation_interval = 0;                           // steps between two evaluations; 0 = the save interval
 };
 
 const char* usage_text() {
@@ -46,7 +50,8 @@ const char* usage_text() {
            "      --initial-learning-rate arg   --learning-rate-shrink-factor arg   --min-learning-rate arg   --save-interval arg\n"
            "  -t, --relative-training-length arg   --max-total-steps arg   -c, --cached-image-count arg   --data-loader-thread-count arg\n"
            "      --no-empty-label-image-warning   --primary-cuda-device arg\n"
-           "  extensions: --host-crops   --devices 0,1,...   --precision bf16|fp32   --seed arg   --hbm-image-budget-gib arg\n";
+           "  extensions: --host-crops   --devices 0,1,...   --precision bf16|fp32   --seed arg   --hbm-image-budget-gib arg\n"
+           "      --validation-directory arg   --validation-interval arg (default: the save interval)   --validation-precision bf16|fp32\n";
 }
 
 TrainSettings read_command_line(int argc, char** argv) {
@@ -76,6 +81,9 @@ TrainSettings read_command_line(int argc, char** argv) {
         {"--precision", [&](const std::string& v) { s.precision = v; }},
         {"--hbm-image-budget-gib", num(s.hbm_budget_gib)},
         {"--seed", [&](const std::string& v) { s.seed = std::stoull(v); s.has_seed = true; }},
+        {"--validation-directory", [&](const std::string& v) { s.validation_directory = v; }},
+        {"--validation-interval", count(s.validation_interval)},
+        {"--validation-precision", [&](const std::string& v) { s.validation_precision = v; }},
         {"--devices", [&](const std::string& v) { std::stringstream list(v); std::string item; while (std::getline(list, item, ',')) s.devices.push_back(std::stoi(item)); }},
     };
     std::map<std::string, bool*> switches = {
@@ -94,6 +102,9 @@ TrainSettings read_command_line(int argc, char** argv) {
     }
     if (s.directory.empty()) throw std::runtime_error("Option 'input-directory' is required but not present");
     if (s.precision != "bf16" && s.precision != "fp32") throw std::runtime_error("--precision must be fp32 or bf16");
+    if (s.validation_precision.empty()) s.validation_precision = s.precision;
+    if (s.validation_precision != "bf16" && s.validation_precision != "fp32") throw std::runtime_error("--validation-precision must be fp32 or bf16");
+    if (s.validation_interval == 0) s.validation_interval = s.save_interval;
     return s;
 }
 
@@ -192,6 +203,70 @@ void save_inference_net(NetPimpl::TrainingNet& trainer, const std::string& class
     if (!out) throw std::runtime_error("Unable to write annonet.dnn");
 }
 
+// ---- held-out evaluation (--validation-directory): images that are never drawn for training, cut ONCE into windows of the training input
+// dimension on a fixed grid from (0, 0) with step `dim` — no random draw, no augmentation; the chip is clamp-to-edge as a training crop's,
+// labels outside the image are "ignore", every weight is 1 — so every labelled pixel of every held-out image is counted exactly once.
+// The windows stay in HBM; an evaluation is one anh_trainer_evaluate_device call (TrainingNet::EvaluateDevice).
+class ValidationSet {
+  public:
+    ValidationSet(const TrainSettings& s, const std::vector<AnnoClass>& classes, int dim) : dim_(dim), precision_(s.validation_precision == "fp32" ? ANH_FP32 : ANH_BF16) {
+        constexpr int C = NetPimpl::kInputChannels;
+        const std::vector<image_filenames_type> files = find_image_files(s.validation_directory, true);
+        std::vector<uint8_t> pixels;
+        std::vector<uint16_t> labels;
+        for (const image_filenames_type& names : files) {
+            sample_type sample = read_sample(names, classes, true, s.initial_downscaling);   // as the training images are read (CropFeeder::decode)
+            if (!sample.error.empty()) throw std::runtime_error(sample.error);
+            ignore_classes_to_ignore(sample, s.ignored_classes);
+            if (std::isfinite(s.region_area) || std::isfinite(s.region_width) || std::isfinite(s.region_height))
+                ignore_large_nonzero_regions(sample, s.region_area, s.region_width, s.region_height);
+            const long H = sample.input_image.nr(), W = sample.input_image.nc();
+            const uint8_t* img = reinterpret_cast<const uint8_t*>(&*sample.input_image.begin());
+            ++images_;
+            for (long top = 0; top < H; top += dim)
+                for (long left = 0; left < W; left += dim) {
+                    const size_t at = windows_++ * (size_t)dim * dim;
+                    pixels.resize((at + (size_t)dim * dim) * C);
+                    labels.resize(at + (size_t)dim * dim);
+                    for (long r = 0; r < dim; ++r) {
+                        const long sy = top + r, cy = std::min(sy, H - 1);
+                        for (long c = 0; c < dim; ++c) {
+                            const long sx = left + c, cx = std::min(sx, W - 1);
+                            for (int ch = 0; ch < C; ++ch) pixels[(at + (size_t)r * dim + c) * C + ch] = img[(cy * W + cx) * C + ch];
+                            labels[at + (size_t)r * dim + c] = (sy == cy && sx == cx) ? sample.label_image(cy, cx) : (uint16_t)dlib::loss_multiclass_log_per_pixel_::label_to_ignore;
+                        }
+                    }
+                }
+        }
+        if (windows_ == 0) throw std::runtime_error("Didn't find an anno dataset in the validation directory " + s.validation_directory);
+        hip(hipMalloc(reinterpret_cast<void**>(&d_images_), pixels.size()), "hipMalloc");
+        hip(hipMalloc(reinterpret_cast<void**>(&d_labels_), labels.size() * sizeof(uint16_t)), "hipMalloc");
+        hip(hipMemcpy(d_images_, pixels.data(), pixels.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        hip(hipMemcpy(d_labels_, labels.data(), labels.size() * sizeof(uint16_t), hipMemcpyHostToDevice), "hipMemcpy");
+        std::cout << "validation images: " << images_ << ", windows of " << dim << " x " << dim << ": " << windows_ << std::endl;
+    }
+    ValidationSet(const ValidationSet&) = delete;
+    ValidationSet& operator=(const ValidationSet&) = delete;
+    ~ValidationSet() { if (d_images_) (void)hipFree(d_images_); if (d_labels_) (void)hipFree(d_labels_); }
+
+    void report(const NetPimpl::TrainingNet& trainer, size_t step) const {
+        const NetPimpl::Evaluation e = trainer.EvaluateDevice(d_images_, d_labels_, nullptr, (int)windows_, dim_, dim_, precision_);
+        std::printf("validation: step %zu  images %zu  windows %zu  loss %.9g  accuracy %.9g  mean_iou %.9g\n", step, images_, windows_, e.MeanLoss(), e.PixelAccuracy(),
+                    e.MeanIoU());
+        std::printf("validation iou per class:");
+        for (double v : e.ClassIoU()) std::printf(" %.9g", v);
+        std::printf("\n");
+        std::fflush(stdout);
+    }
+
+  private:
+    static void hip(hipError_t e, const char* what) { if (e != hipSuccess) throw std::runtime_error(std::string(what) + " of the validation windows: " + hipGetErrorString(e)); }
+    const int dim_, precision_;
+    size_t images_ = 0, windows_ = 0;
+    uint8_t* d_images_ = nullptr;
+    uint16_t* d_labels_ = nullptr;
+};
+
 int run(const TrainSettings& s) {
     const double relative_length = std::max(0.01, s.relative_length);
     std::cout << "Allow flipping input images upside down = " << (s.flip_ud ? "yes" : "no") << std::endl;
@@ -243,6 +318,8 @@ int run(const TrainSettings& s) {
     if (files.empty()) { std::cout << "Didn't find an anno dataset. " << std::endl; return 1; }
     std::cout << std::endl << "Now training..." << std::endl;
 
+    std::unique_ptr<ValidationSet> validation;
+    if (!s.validation_directory.empty()) validation = std::make_unique<ValidationSet>(s, classes, crop_side);
     CropFeeder feeder(s, files, classes, crop_side, device_crops);
     // device path: full images uploaded on first sight and kept in HBM — within a byte budget (--hbm-image-budget-gib): the least
     // recently drawn image leaves when a new one would not fit, as the decoded images leave the reference's LRU cache
@@ -298,7 +375,9 @@ int run(const TrainSettings& s) {
             if (device_crops) trainer.StartTrainingOnCrops(hbm_images, specs, crop_side, s.class_weight, s.image_weight);
             else trainer.StartTraining(images, labels);
             if (step++ % s.save_interval == 0) save_inference_net(trainer, classes_json, total_downscaling);
+            if (validation && step % s.validation_interval == 0) validation->report(trainer, step);
         }
+        if (validation) { std::cout.flush(); validation->report(trainer, step); }   // once more after the last step
     } catch (std::exception& e) {   // in-loop errors: print and leave with 2 (:616-620)
         std::cout << e.what() << std::endl;
         feeder.stop();

@@ -340,6 +340,23 @@ class RuntimeNet(_Profiled):
         check(self.L.anh_runtime_layer_tensor(self.h, layer, _ptr(out), out.size, dims))
         return out
 
+    def evaluate(self, samples, labels, gains=None, want_predicted=False):
+        """anh_runtime_evaluate on host samples: a list of u8 [H,W,C] and a list of (label, weight) arrays as set_weights() returns
+        them -> EvalResult"""
+        imgs, labs, ip, lp, n, h, w = _eval_samples(samples, labels)
+        per_image, confusion = _eval_outputs(n, self.cfg.classes, None)
+        predicted = np.empty((n, h, w), np.uint16) if want_predicted else None
+        check(self.L.anh_runtime_evaluate(self.h, ip, lp, n, h, w, _ptr(_eval_gains(gains, self.cfg.classes)), _ptr(per_image), _ptr(confusion), _ptr(predicted)))
+        return EvalResult(per_image, confusion, predicted)
+
+    def evaluate_device(self, d_images_ptr, d_labels_ptr, d_weights_ptr, n, height, width, gains=None, d_predicted_ptr=0, prefill=None):
+        """anh_runtime_evaluate_device on resident windows [n,H,W,C] u8, labels [n,H,W] u16 and weights [n,H,W] fp32 (0 = ones), device
+        pointers as ints -> EvalResult (the predicted maps stay on the device, at d_predicted_ptr)"""
+        per_image, confusion = _eval_outputs(n, self.cfg.classes, prefill)
+        check(self.L.anh_runtime_evaluate_device(self.h, d_images_ptr or None, d_labels_ptr or None, d_weights_ptr or None, n, height, width,
+                                                 _ptr(_eval_gains(gains, self.cfg.classes)), _ptr(per_image), _ptr(confusion), d_predicted_ptr or None))
+        return EvalResult(per_image, confusion)
+
 
 # ---- what the inference wrappers share: their arguments as the C ABI takes them ----
 def _f64(values):
@@ -804,6 +821,73 @@ def score(truth_map, result_map, classes, prefill=None, net=None):
     return pp[0], pr[0], int(lab[0])
 
 
+# ---- held-out evaluation: loss sums and confusion counts per window (anh_eval_logits_device, anh_runtime_evaluate*, anh_trainer_evaluate*) ----
+EVAL_DTYPE = np.dtype([("loss_sum", np.float64), ("weight_sum", np.float64), ("counted", np.uint64), ("unclassified", np.uint64)])   # anh_eval_image
+
+
+class EvalResult:
+    """What an evaluation call returns: per_image [n] (EVAL_DTYPE), confusion [n,K,K] u64 (first index ground truth) and, where the call
+    was asked for it, predicted [n,H,W] u16."""
+
+    def __init__(self, per_image, confusion, predicted=None):
+        self.per_image, self.confusion, self.predicted = per_image, confusion, predicted
+
+    def matrix(self):
+        return self.confusion.sum(axis=0, dtype=np.uint64)
+
+    def mean_loss(self):
+        return float(self.per_image["loss_sum"].sum() / self.per_image["weight_sum"].sum())
+
+    def pixel_accuracy(self):
+        return float(np.trace(self.matrix())) / float(self.per_image["counted"].sum())
+
+    def class_iou(self):
+        """per class: hits / (pixels of the class in the truth + predicted as the class - hits); nan for a class that never occurs"""
+        m = self.matrix().astype(np.float64)
+        hits = np.diag(m)
+        union = m.sum(axis=1) + m.sum(axis=0) - hits
+        return np.where(union > 0, hits / np.where(union > 0, union, 1.0), np.nan)
+
+
+def _eval_outputs(n, classes, prefill):
+    """per_image [n] and confusion [n,K,K]; `prefill`: byte they are filled with before the call (tests: every element is overwritten)"""
+    fill = 0 if prefill is None else int(prefill) & 255
+    per_image = np.full(max(n, 0) * EVAL_DTYPE.itemsize, fill, np.uint8).view(EVAL_DTYPE)
+    confusion = np.full(max(n, 0) * max(classes, 0) ** 2 * 8, fill, np.uint8).view(np.uint64).reshape(max(n, 0), max(classes, 0), max(classes, 0))
+    return per_image, confusion
+
+
+def _eval_gains(gains, classes):
+    g = _f64(gains)
+    if g is not None and g.size != classes:
+        raise AnnonetHipError(1, "gains need one value per class")
+    return g
+
+
+def _eval_samples(samples, labels):
+    """host samples as StartTraining takes them -> (image arrays, label arrays, their pointer lists, n, H, W)"""
+    n = len(samples)
+    if n == 0 or n != len(labels):
+        raise AnnonetHipError(1, "samples and labels must be non-empty and of equal length")
+    imgs = [np.ascontiguousarray(s, dtype=np.uint8) for s in samples]
+    labs = [np.ascontiguousarray(l) for l in labels]
+    h, w = imgs[0].shape[:2]
+    for im, lb in zip(imgs, labs):
+        if im.shape[:2] != (h, w) or lb.shape != (h, w) or lb.itemsize != C.sizeof(_lib.WLabel):
+            raise AnnonetHipError(1, "all samples and weighted label images of a call must share one size")
+    return imgs, labs, (C.c_void_p * n)(*[im.ctypes.data for im in imgs]), (C.c_void_p * n)(*[lb.ctypes.data for lb in labs]), n, h, w
+
+
+def eval_logits_device(net, d_logits_ptr, d_labels_ptr, d_weights_ptr, n, classes, height, width, gains=None, d_predicted_ptr=0, prefill=None):
+    """anh_eval_logits_device: the tally alone on resident fp32 logits [n,K,H,W], u16 labels [n,H,W] and fp32 weights [n,H,W] (0 = ones),
+    device pointers as ints, on the handle's stream -> EvalResult (the predicted maps stay on the device, at d_predicted_ptr)."""
+    per_image, confusion = _eval_outputs(n, classes, prefill)
+    g = _eval_gains(gains, classes)
+    check(net.L.anh_eval_logits_device(net.h, d_logits_ptr or None, d_labels_ptr or None, d_weights_ptr or None, n, classes, height, width, _ptr(g),
+                                       _ptr(per_image), _ptr(confusion), d_predicted_ptr or None))
+    return EvalResult(per_image, confusion)
+
+
 def _regions_outputs(out, tables, wanted):
     """(results..., tables) followed by the optional lists that were asked for"""
     return tuple(out) + (tables,) + tuple(arrays for want, arrays in wanted if want)
@@ -1030,6 +1114,26 @@ class TrainingNet(_Profiled):
         h = C.c_void_p()
         check(self.L.anh_trainer_snapshot_runtime(self.h, self.cfg.precision if precision is None else precision, C.byref(h)))
         return RuntimeNet(_handle=h)
+
+    def evaluate(self, samples, labels, precision=None, gains=None, want_predicted=False):
+        """anh_trainer_evaluate: RuntimeNet.evaluate with the parameters as they stand after the last step, on the inference net the
+        handle keeps for it; the training state is left untouched"""
+        imgs, labs, ip, lp, n, h, w = _eval_samples(samples, labels)
+        K = self.cfg.classes
+        per_image, confusion = _eval_outputs(n, K, None)
+        predicted = np.empty((n, h, w), np.uint16) if want_predicted else None
+        check(self.L.anh_trainer_evaluate(self.h, self.cfg.precision if precision is None else precision, ip, lp, n, h, w, _ptr(_eval_gains(gains, K)),
+                                          _ptr(per_image), _ptr(confusion), _ptr(predicted)))
+        return EvalResult(per_image, confusion, predicted)
+
+    def evaluate_device(self, d_images_ptr, d_labels_ptr, d_weights_ptr, n, height, width, precision=None, gains=None, d_predicted_ptr=0, prefill=None):
+        """anh_trainer_evaluate_device: the same on windows resident on the trainer's first device (see RuntimeNet.evaluate_device)"""
+        K = self.cfg.classes
+        per_image, confusion = _eval_outputs(n, K, prefill)
+        check(self.L.anh_trainer_evaluate_device(self.h, self.cfg.precision if precision is None else precision, d_images_ptr or None, d_labels_ptr or None,
+                                                 d_weights_ptr or None, n, height, width, _ptr(_eval_gains(gains, K)), _ptr(per_image), _ptr(confusion),
+                                                 d_predicted_ptr or None))
+        return EvalResult(per_image, confusion)
 
     def save_state(self, path):
         check(self.L.anh_trainer_save_state(self.h, path.encode()))

@@ -20,8 +20,10 @@
 
 #include <chrono>
 #include <cstdint>
+#include <algorithm>
 #include <istream>
 #include <iterator>
+#include <limits>
 #include <ostream>
 #include <stdexcept>
 #include <string>
@@ -106,6 +108,71 @@ class OutputTensor {
     int k_ = 0, nr_ = 0, nc_ = 0;
 };
 
+// Extension (no counterpart in dlib-dnn-pimpl-wrapper): what RuntimeNet::Evaluate / TrainingNet::Evaluate return — per window the loss
+// sums and counts of anh_eval_image and the confusion matrix [truth][predicted] (annonet_hip.h, "held-out evaluation"), with the figures
+// a training run prints.
+struct Evaluation {
+    int classes = 0;
+    std::vector<anh_eval_image> per_image;
+    std::vector<uint64_t> confusion;   // [images][classes][classes]
+    size_t images() const { return per_image.size(); }
+    std::vector<uint64_t> Matrix() const {   // the images' matrices added up
+        std::vector<uint64_t> m((size_t)classes * classes, 0);
+        for (size_t i = 0; i < confusion.size(); ++i) m[i % m.size()] += confusion[i];
+        return m;
+    }
+    uint64_t Counted() const { uint64_t n = 0; for (const anh_eval_image& e : per_image) n += e.counted; return n; }
+    double MeanLoss() const {   // sum loss_sum / sum weight_sum
+        double loss = 0, weight = 0;
+        for (const anh_eval_image& e : per_image) { loss += e.loss_sum; weight += e.weight_sum; }
+        return loss / weight;
+    }
+    double PixelAccuracy() const {   // trace / sum counted
+        const std::vector<uint64_t> m = Matrix();
+        uint64_t trace = 0;
+        for (int c = 0; c < classes; ++c) trace += m[(size_t)c * classes + c];
+        return (double)trace / (double)Counted();
+    }
+    std::vector<double> ClassIoU() const {   // hits / (truth + predicted - hits); NaN for a class that occurs on neither side
+        const std::vector<uint64_t> m = Matrix();
+        std::vector<double> iou((size_t)classes);
+        for (int c = 0; c < classes; ++c) {
+            uint64_t truth = 0, predicted = 0;
+            for (int o = 0; o < classes; ++o) { truth += m[(size_t)c * classes + o]; predicted += m[(size_t)o * classes + c]; }
+            const uint64_t hits = m[(size_t)c * classes + c], all = truth + predicted - hits;
+            iou[(size_t)c] = all ? (double)hits / (double)all : std::numeric_limits<double>::quiet_NaN();
+        }
+        return iou;
+    }
+    double MeanIoU() const {   // over the classes that occur
+        double sum = 0; int n = 0;
+        for (double v : ClassIoU()) if (v == v) { sum += v; ++n; }
+        return n ? sum / n : std::numeric_limits<double>::quiet_NaN();
+    }
+};
+
+namespace detail {
+inline void sample_pointers(const std::vector<input_type>& samples, const std::vector<training_label_type>& labels, std::vector<const uint8_t*>& ip,
+                            std::vector<const anh_wlabel*>& lp, long& nr, long& nc) {
+    if (samples.empty() || samples.size() != labels.size()) throw std::runtime_error("annonet_hip: samples and labels must be non-empty and of equal size");
+    ip.resize(samples.size()); lp.resize(samples.size());
+    nr = samples[0].nr(); nc = samples[0].nc();
+    for (size_t i = 0; i < samples.size(); ++i) {
+        if (samples[i].nr() != nr || samples[i].nc() != nc || labels[i].nr() != nr || labels[i].nc() != nc)
+            throw std::runtime_error("annonet_hip: all samples and label images of a call must share one size");
+        ip[i] = reinterpret_cast<const uint8_t*>(&*samples[i].begin());
+        lp[i] = reinterpret_cast<const anh_wlabel*>(&*labels[i].begin());
+    }
+}
+inline Evaluation evaluation_for(int classes, size_t n) {
+    Evaluation e;
+    e.classes = classes;
+    e.per_image.resize(n);
+    e.confusion.resize(n * (size_t)classes * classes);
+    return e;
+}
+}  // namespace detail
+
 class RuntimeNet {
   public:
     RuntimeNet() = default;
@@ -134,9 +201,32 @@ class RuntimeNet {
         reset();
         check(anh_runtime_deserialize(blob.data(), blob.size(), precision, &h_));
     }
+    // Extension: held-out evaluation of host samples (anh_runtime_evaluate) / of n windows resident in HBM (anh_runtime_evaluate_device);
+    // gains: one value per class, or empty
+    Evaluation Evaluate(const std::vector<input_type>& samples, const std::vector<training_label_type>& labels, const std::vector<double>& gains = {}) const {
+        require();
+        std::vector<const uint8_t*> ip; std::vector<const anh_wlabel*> lp; long nr, nc;
+        detail::sample_pointers(samples, labels, ip, lp, nr, nc);
+        Evaluation e = detail::evaluation_for(classes(gains), samples.size());
+        check(anh_runtime_evaluate(h_, ip.data(), lp.data(), (int)samples.size(), (int)nr, (int)nc, gains.empty() ? nullptr : gains.data(), e.per_image.data(),
+                                   e.confusion.data(), nullptr));
+        return e;
+    }
+    Evaluation EvaluateDevice(const uint8_t* d_images, const uint16_t* d_labels, const float* d_weights, int n, int nr, int nc, const std::vector<double>& gains = {}) const {
+        require();
+        Evaluation e = detail::evaluation_for(classes(gains), (size_t)std::max(n, 0));
+        check(anh_runtime_evaluate_device(h_, d_images, d_labels, d_weights, n, nr, nc, gains.empty() ? nullptr : gains.data(), e.per_image.data(), e.confusion.data(), nullptr));
+        return e;
+    }
     anh_runtime* handle() const { return h_; }
 
   private:
+    int classes(const std::vector<double>& gains) const {
+        anh_net_config cfg;
+        check(anh_runtime_config(h_, &cfg));
+        if (!gains.empty() && (int)gains.size() != cfg.classes) throw std::runtime_error("annonet_hip: gains need one value per class");
+        return cfg.classes;
+    }
     void require() const { if (!h_) throw std::runtime_error("annonet_hip: RuntimeNet holds no network (Deserialize it or take it from TrainingNet::GetRuntimeNet)"); }
     void reset() { if (h_) anh_runtime_destroy(h_); h_ = nullptr; }
     void copy_from(const RuntimeNet& o) {
@@ -228,9 +318,33 @@ class TrainingNet {
         check(anh_trainer_snapshot_runtime(h_, precision, &rt));
         return RuntimeNet(rt);
     }
+    // Extension: held-out evaluation in the middle of a run (anh_trainer_evaluate / anh_trainer_evaluate_device): the weights as they stand
+    // after the last step, on an inference net of `precision` the trainer keeps for it; the training state is left untouched
+    Evaluation Evaluate(const std::vector<input_type>& samples, const std::vector<training_label_type>& labels, int precision = ANH_BF16,
+                        const std::vector<double>& gains = {}) const {
+        std::vector<const uint8_t*> ip; std::vector<const anh_wlabel*> lp; long nr, nc;
+        detail::sample_pointers(samples, labels, ip, lp, nr, nc);
+        Evaluation e = detail::evaluation_for(classes(gains), samples.size());
+        check(anh_trainer_evaluate(h_, precision, ip.data(), lp.data(), (int)samples.size(), (int)nr, (int)nc, gains.empty() ? nullptr : gains.data(),
+                                   e.per_image.data(), e.confusion.data(), nullptr));
+        return e;
+    }
+    Evaluation EvaluateDevice(const uint8_t* d_images, const uint16_t* d_labels, const float* d_weights, int n, int nr, int nc, int precision = ANH_BF16,
+                              const std::vector<double>& gains = {}) const {
+        Evaluation e = detail::evaluation_for(classes(gains), (size_t)std::max(n, 0));
+        check(anh_trainer_evaluate_device(h_, precision, d_images, d_labels, d_weights, n, nr, nc, gains.empty() ? nullptr : gains.data(), e.per_image.data(),
+                                          e.confusion.data(), nullptr));
+        return e;
+    }
     anh_trainer* handle() const { return h_; }
 
   private:
+    int classes(const std::vector<double>& gains) const {
+        anh_net_config cfg;
+        check(anh_trainer_config(h_, &cfg));
+        if (!gains.empty() && (int)gains.size() != cfg.classes) throw std::runtime_error("annonet_hip: gains need one value per class");
+        return cfg.classes;
+    }
     anh_trainer* h_ = nullptr;
 };
 

@@ -339,6 +339,37 @@ int anh_score_batch(anh_runtime* h, const uint16_t* const* truth, const uint16_t
 /* n = 1, host maps */
 int anh_score(anh_runtime* h, const uint16_t* truth, const uint16_t* result, int classes, int height, int width,
               uint64_t* per_pixel, uint64_t* per_region, uint64_t* labelled);
+/* ---- held-out evaluation: the loss the trainer optimises and the confusion counts of the inference program's argmax, from the logits
+ * of an inference-mode forward (bn folded from the running statistics), per window ("image") ----
+ * For every pixel with logits z[0..K), label y and weight w:
+ *   predicted     find_label (annonet_infer.cpp:170-185) on z with the gains: the first class with the strictly largest
+ *                 (float)((double)z + gain); 65535 when no class exceeds -inf (every logit NaN or -inf).  A predicted map, when asked for,
+ *                 receives it for every pixel, labelled or not.
+ *   y == ANH_LABEL_IGNORE: the pixel is skipped.  Another y >= K: the call returns ANH_ERR_INVALID and its outputs are unspecified.
+ *   counted       += 1; where predicted == 65535: unclassified += 1 and nothing else; otherwise
+ *   confusion[y][predicted] += 1, weight_sum += w, loss_sum += w * (-log max(softmax(z)[y], 1e-10)) — the term of
+ *                 loss_multiclass_log_per_pixel_weighted as the training step computes it (float max, expf, float sum, z / sum, logf;
+ *                 product and accumulation in double), without the gains.
+ * So the sum of an image's confusion matrix plus unclassified equals counted; mean loss = sum loss_sum / sum weight_sum, pixel accuracy =
+ * trace / sum counted.  Pixels where some but not all logits are NaN are unspecified.
+ * All outputs are per image and OVERWRITTEN: per_image [n]; confusion [n][K][K] u64 (first index ground truth) or NULL; d_predicted /
+ * predicted [n][H][W] u16 or NULL.  gains: K host doubles or NULL.  weights NULL = 1 everywhere.  K <= 64 (the net's limit).
+ * The counts are integer atomics; the double sums are fixed-order sums of per-workgroup partials, and how an image is cut into workgroups
+ * depends on its size alone: image i of any call equals the call on that image alone bit for bit, on every run, wherever its maps lie.
+ * The calls run on the handle's stream (replica 0 of a handle with several) and wait on the host once, for the results.  Everything a
+ * call needs is reserved before its first kernel: one that does not fit returns ANH_ERR_OOM and leaves the handle usable. */
+typedef struct { double loss_sum, weight_sum; uint64_t counted, unclassified; } anh_eval_image;
+/* the tally alone, on resident logits [n][classes][height][width] fp32 (what anh_runtime_forward_device writes), d_labels [n][H][W] u16,
+ * d_weights [n][H][W] fp32 or NULL; `classes` need not be the net's */
+int anh_eval_logits_device(anh_runtime* h, const float* d_logits, const uint16_t* d_labels, const float* d_weights, int n, int classes, int height, int width,
+                           const double* gains, anh_eval_image* per_image, uint64_t* confusion, uint16_t* d_predicted);
+/* n windows of one size, d_images [n][H][W][C] resident (the sizes anh_runtime_forward_device accepts): cut into forward batches no larger
+ * than an inference tile batch, each followed by the tally on its logits; image i does not depend on the cut */
+int anh_runtime_evaluate_device(anh_runtime* h, const uint8_t* d_images, const uint16_t* d_labels, const float* d_weights, int n, int height, int width,
+                                const double* gains, anh_eval_image* per_image, uint64_t* confusion, uint16_t* d_predicted);
+/* host samples as anh_trainer_step takes them: images[i] height*width*channels u8, labels[i] height*width weighted labels */
+int anh_runtime_evaluate(anh_runtime* h, const uint8_t* const* images, const anh_wlabel* const* labels, int n, int height, int width,
+                         const double* gains, anh_eval_image* per_image, uint64_t* confusion, uint16_t* predicted);
 /* label rows [row0, row1) of device-resident blended planes (find_label, annonet_infer.cpp:170-185): the second half of a
    sharded annonet_infer(), run after the ranks have exchanged the plane sums of their overlapping tiles */
 int anh_argmax_device(anh_runtime* h, const float* d_blended, int height, int width, int row0, int row1, const double* gains, uint16_t* d_result);
@@ -398,6 +429,17 @@ int anh_trainer_get_momentum(anh_trainer* h, float* momentum, int64_t n_params);
 int anh_trainer_set_momentum(anh_trainer* h, const float* momentum, int64_t n_params);
 /* GetRuntimeNet() (annonet_train_main.cpp:558): independent by-value snapshot; quiesces the device first */
 int anh_trainer_snapshot_runtime(anh_trainer* h, int precision, anh_runtime** out);
+/* Held-out evaluation in the middle of a training run (see anh_runtime_evaluate): the parameters and running statistics as they stand
+ * after the last step issued — a step in flight finishes first — go into an inference net of `precision` that the handle keeps for
+ * this purpose (made on first use on the trainer's first device, like a snapshot, and refreshed on every call), which evaluates the
+ * samples.  The result equals anh_trainer_snapshot_runtime followed by anh_runtime_evaluate / _evaluate_device, bit for bit.  Nothing of
+ * the training state is touched: parameters, momentum, running statistics and their update counts, step count, the losses in flight and
+ * the learning-rate history, the accumulator tables, the step's streams and events.  On a handle with several replicas the evaluation
+ * runs on replica 0's device only.  The _device form takes pointers resident on that device. */
+int anh_trainer_evaluate(anh_trainer* h, int precision, const uint8_t* const* images, const anh_wlabel* const* labels, int n, int height, int width,
+                         const double* gains, anh_eval_image* per_image, uint64_t* confusion, uint16_t* predicted);
+int anh_trainer_evaluate_device(anh_trainer* h, int precision, const uint8_t* d_images, const uint16_t* d_labels, const float* d_weights, int n, int height,
+                                int width, const double* gains, anh_eval_image* per_image, uint64_t* confusion, uint16_t* d_predicted);
 int anh_trainer_save_state(anh_trainer* h, const char* path); /* trainer synchronization file */
 int anh_trainer_load_state(anh_trainer* h, const char* path);
 int anh_trainer_set_stream(anh_trainer* h, void* hip_stream);
