@@ -12,4 +12,4 @@ from .netpimpl import (Dataset, RuntimeNet, TrainingNet, REGION_DTYPE, argmax_de
                        op_conv_backward_data, op_conv_backward_data_bn, op_conv_backward_filter, op_conv_backward_filter_bn,
                        op_conv_forward, op_conv_forward_stats, outpaint,
                        op_bn_backward, op_bn_fold, op_bn_forward_stats, op_conv_backward_data_bn_table, op_conv_forward_stats_table, op_head_train, op_loss,
-                       random_rect_containing_point, resize_image, resize_labels, resize_image_batch, resize_labels_batch, scaled_dims, set_devices, set_weights, shard_range, cross_replica_overlaps, tiling)
+                       random_rect_containing_point, resolve_pick, resize_image, resize_labels, resize_image_batch, resize_labels_batch, scaled_dims, set_devices, set_weights, shard_range, cross_replica_overlaps, tiling)

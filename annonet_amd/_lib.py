@@ -63,6 +63,18 @@ class CropSpec(C.Structure):   # anh_crop_spec
                 ("color_offset", C.c_int * 3)]
 
 
+class DatasetInfo(C.Structure):   # anh_dataset_info
+    _fields_ = [("ignored_by_class", C.c_int64), ("ignored_by_size", C.c_int64), ("present", C.c_int), ("classes", C.c_uint16 * 64), ("counts", C.c_uint64 * 64)]
+
+
+class CropDraw(C.Structure):   # anh_crop_draw
+    _fields_ = [("class_draw", C.c_uint32), ("point_draw", C.c_uint64), ("rect_draw_x", C.c_uint32), ("rect_draw_y", C.c_uint32)]
+
+
+class CropPick(C.Structure):   # anh_crop_pick
+    _fields_ = [("label", C.c_uint16), ("x", C.c_int32), ("y", C.c_int32), ("left", C.c_long), ("top", C.c_long)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("type", "k", "stride", "pad", "cin", "cout")]
 
@@ -267,6 +279,14 @@ _SIGNATURES = {  # ConvDesc / OpInput are defined above
     "anh_dataset_resident_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "anh_dataset_crop_batch": (C.c_int, [C.c_void_p, C.POINTER(CropSpec), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P]),
     "anh_trainer_step_crops": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CropSpec), C.c_int, C.c_int, C.c_double, C.c_double]),
+    "anh_dataset_prepare": (C.c_int, [C.c_void_p, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(DatasetInfo)]),
+    "anh_dataset_scratch_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "anh_dataset_labels": (C.c_int, [C.c_void_p, C.c_int, _P]),
+    "anh_resolve_pick": (C.c_int, [C.POINTER(DatasetInfo), C.c_uint32, C.c_uint64, C.POINTER(C.c_uint16), C.POINTER(C.c_uint64)]),
+    "anh_dataset_pick": (C.c_int, [C.c_void_p, C.POINTER(CropSpec), C.POINTER(CropDraw), C.c_int, C.c_int, C.POINTER(CropPick)]),
+    "anh_dataset_crop_batch_picked": (C.c_int, [C.c_void_p, C.POINTER(CropSpec), C.POINTER(CropDraw), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P,
+                                                C.POINTER(CropPick)]),
+    "anh_trainer_step_crops_picked": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CropSpec), C.POINTER(CropDraw), C.c_int, C.c_int, C.c_double, C.c_double]),
     "anh_dnn_envelope_pack": (C.c_int, [C.c_char_p, C.c_size_t, C.c_double, _P, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "anh_dnn_envelope_unpack": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_double),
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),

@@ -219,57 +219,105 @@ struct anh_trainer {
 // Full images of a dataset, resident in HBM, plus the scratch of the device crop path.
 struct anh_dataset {
     int channels = 3;
-    struct Item { DevBuf image, labels; int height = 0, width = 0; };
+    // prepared: anh_dataset_prepare has built the point index of the labels as they stand (index: one row of `blocks` words per present
+    // class, in info.classes order — the class's pixel count in the blocks before each block)
+    struct Item { DevBuf image, labels, index; int height = 0, width = 0; bool prepared = false; uint64_t index_bytes = 0; anh_dataset_info info{}; };
     std::vector<Item> items;          // a removed image leaves an empty slot (height 0) that a later add reuses
     std::vector<int> free_slots;
     uint64_t resident_bytes = 0;
     Stream stream;
-    DevBuf d_specs, d_hist, d_first, d_table, d_bad;
+    DevBuf d_specs, d_hist, d_first, d_table, d_bad, d_jobs, d_picks;
+    DevBuf prep_counts, prep_words, blob_parent, blob_map, blob_sums, blob_table;   // scratch of anh_dataset_prepare
     PinnedBuf pinned;
     DevBuf out;   // outputs of the host-array form
     ~anh_dataset() { if (stream.get()) (void)hipStreamSynchronize(stream.get()); }
-    // Cuts n crops into device arrays on `stream`.  One host round trip inside: the per-crop label histograms come back,
-    // set_weights' table is computed with the host's own arithmetic (bit-identical to set_weights on the crop) and goes up.
-    void crop_batch(const anh_crop_spec* specs, int n, int dim, int classes, double cw, double iw, uint8_t* d_images, uint16_t* d_labels, float* d_weights) {
+    Item& item(int index, const char* what) {
+        if (!(index >= 0 && (size_t)index < items.size() && items[(size_t)index].height > 0)) fail(ANH_ERR_INVALID, std::string(what) + ": image index out of range (or removed)");
+        return items[(size_t)index];
+    }
+    void drop_index(Item& it) { resident_bytes -= it.index_bytes; it.index.release(); it.index_bytes = 0; it.prepared = false; it.info = anh_dataset_info{}; }
+
+    // What a crop batch stages in ONE pinned block: the kernel's specs, the histograms that come back, the weight tables that go up, the
+    // two error words and, for picked crops, the pick jobs that go up and the picks that may come back.
+    struct Staged {
+        size_t spec_bytes, tab;
+        CropSource* hs; unsigned* h_hist; unsigned* h_first; float* h_table; int* h_bad; DatasetPickJob* h_jobs; DatasetPick* h_picks;
+    };
+    // Validates the specs, fills and uploads the kernel's specs on `stream`.  draws != nullptr: the rectangle's corner does not come from
+    // the spec: the host resolves (class, k) from the info kept at prepare time and ONE launch picks the pixel and writes the corner
+    // into the uploaded specs.
+    Staged stage_specs(const anh_crop_spec* specs, const anh_crop_draw* draws, int n, int dim) {
         ANH_REQUIRE(specs && n >= 1 && dim >= 1 && dim <= 32768, "crop batch: bad argument");
-        ANH_REQUIRE(classes >= 1 && classes <= kCropMaxClasses, "crop batch: class count must be 1..64");
-        const size_t spec_bytes = (size_t)n * sizeof(CropSource), tab = (size_t)n * kCropMaxClasses * 4;
-        const size_t need = spec_bytes + 3 * tab + 64;
+        Staged g;
+        g.spec_bytes = (size_t)n * sizeof(CropSource); g.tab = (size_t)n * kCropMaxClasses * 4;
+        const size_t jobs_off = g.spec_bytes + 3 * g.tab + 64, picks_off = jobs_off + (size_t)n * sizeof(DatasetPickJob);
+        const size_t need = draws ? picks_off + (size_t)n * sizeof(DatasetPick) : jobs_off;
         const hipStream_t st = stream.get();
         if (need > pinned.bytes) { HIP_CHECK(hipStreamSynchronize(st)); pinned.reserve(need); }
-        d_specs.reserve(spec_bytes); d_hist.reserve(tab); d_first.reserve(tab); d_table.reserve(tab); d_bad.reserve(4);
+        d_specs.reserve(g.spec_bytes); d_hist.reserve(g.tab); d_first.reserve(g.tab); d_table.reserve(g.tab); d_bad.reserve(8);
+        if (draws) { d_jobs.reserve((size_t)n * sizeof(DatasetPickJob)); d_picks.reserve((size_t)n * sizeof(DatasetPick)); }
         char* pin = pinned.as<char>();
-        CropSource* hs = reinterpret_cast<CropSource*>(pin);
-        unsigned* h_hist = reinterpret_cast<unsigned*>(pin + spec_bytes);
-        unsigned* h_first = reinterpret_cast<unsigned*>(pin + spec_bytes + tab);
-        float* h_table = reinterpret_cast<float*>(pin + spec_bytes + 2 * tab);
-        int* h_bad = reinterpret_cast<int*>(pin + spec_bytes + 3 * tab);
+        g.hs = reinterpret_cast<CropSource*>(pin);
+        g.h_hist = reinterpret_cast<unsigned*>(pin + g.spec_bytes);
+        g.h_first = reinterpret_cast<unsigned*>(pin + g.spec_bytes + g.tab);
+        g.h_table = reinterpret_cast<float*>(pin + g.spec_bytes + 2 * g.tab);
+        g.h_bad = reinterpret_cast<int*>(pin + g.spec_bytes + 3 * g.tab);
+        g.h_jobs = reinterpret_cast<DatasetPickJob*>(pin + jobs_off);
+        g.h_picks = reinterpret_cast<DatasetPick*>(pin + picks_off);
         for (int i = 0; i < n; ++i) {
             const anh_crop_spec& c = specs[i];
             ANH_REQUIRE(c.image >= 0 && (size_t)c.image < items.size() && items[(size_t)c.image].height > 0, "crop batch: image index out of range (or removed)");
-            ANH_REQUIRE(c.left > -(1L << 30) && c.left < (1L << 30) && c.top > -(1L << 30) && c.top < (1L << 30), "crop batch: rectangle out of range");
+            if (!draws) ANH_REQUIRE(c.left > -(1L << 30) && c.left < (1L << 30) && c.top > -(1L << 30) && c.top < (1L << 30), "crop batch: rectangle out of range");
             ANH_REQUIRE(c.brightness_change >= 0, "crop batch: negative brightness change");
             const Item& it = items[(size_t)c.image];
             ANH_REQUIRE(c.further_downscaling_factor == 0.0 || (c.further_downscaling_factor >= 1.0 && c.further_downscaling_factor <= 64.0), "crop batch: further downscaling factor must be >= 1");
             ANH_REQUIRE(c.noise_level >= 0 && c.noise_level <= 255, "crop batch: noise level must be 0..255");
             const double f = c.further_downscaling_factor == 0.0 ? 1.0 : c.further_downscaling_factor;
             const int src_dim = (int)std::round(dim * f);   // dim_before_downscaling (annonet_train_main.cpp:127)
-            hs[i] = CropSource{it.image.as<uint8_t>(), it.labels.as<uint16_t>(), it.height, it.width, (int)c.left, (int)c.top,
-                               c.flip_left_right ? 1 : 0, c.flip_upside_down ? 1 : 0, c.brightness_change, src_dim, c.noise_level,
-                               (unsigned long long)c.noise_seed, {c.color_offset[0], c.color_offset[1], c.color_offset[2]}};
+            g.hs[i] = CropSource{it.image.as<uint8_t>(), it.labels.as<uint16_t>(), it.height, it.width, draws ? 0 : (int)c.left, draws ? 0 : (int)c.top,
+                                 c.flip_left_right ? 1 : 0, c.flip_upside_down ? 1 : 0, c.brightness_change, src_dim, c.noise_level,
+                                 (unsigned long long)c.noise_seed, {c.color_offset[0], c.color_offset[1], c.color_offset[2]}};
+            if (draws) {
+                ANH_REQUIRE(it.prepared && it.info.present >= 1, "picked crops: the image has not been prepared (anh_dataset_prepare) or has no labelled pixel");
+                uint16_t label; uint64_t k;
+                const int slot = resolve_pick(it.info, draws[i].class_draw, draws[i].point_draw, &label, &k);
+                const size_t blocks = dataset_index_blocks((int64_t)it.height * it.width);
+                g.h_jobs[i] = DatasetPickJob{it.labels.as<uint16_t>(), it.index.as<unsigned>() + (size_t)slot * blocks, (long long)it.height * it.width, it.width, (int)blocks,
+                                             (unsigned)k, draws[i].rect_draw_x, draws[i].rect_draw_y, src_dim, label};
+            }
         }
-        HIP_CHECK(hipMemcpyAsync(d_specs.p, hs, spec_bytes, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemsetAsync(d_bad.p, 0, 4, st));
+        HIP_CHECK(hipMemcpyAsync(d_specs.p, g.hs, g.spec_bytes, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemsetAsync(d_bad.p, 0, 8, st));
+        if (draws) {
+            HIP_CHECK(hipMemcpyAsync(d_jobs.p, g.h_jobs, (size_t)n * sizeof(DatasetPickJob), hipMemcpyHostToDevice, st));
+            launch_dataset_pick(d_jobs.as<DatasetPickJob>(), n, d_specs.as<CropSource>(), d_picks.as<DatasetPick>(), d_bad.as<int>() + 1, st);
+        }
+        return g;
+    }
+    static void picks_to_host(const Staged& g, const DatasetPickJob* jobs, int n, anh_crop_pick* out) {
+        for (int i = 0; i < n; ++i) out[i] = anh_crop_pick{jobs[i].label, g.h_picks[i].x, g.h_picks[i].y, (long)g.h_picks[i].left, (long)g.h_picks[i].top};
+    }
+    // Cuts n crops into device arrays on `stream`.  One host round trip inside: the per-crop label histograms come back,
+    // set_weights' table is computed with the host's own arithmetic (bit-identical to set_weights on the crop) and goes up.
+    // draws (nullable): see stage_specs; picks (nullable, with draws): the picked pixels and corners, which ride back with the histograms.
+    void crop_batch(const anh_crop_spec* specs, const anh_crop_draw* draws, int n, int dim, int classes, double cw, double iw, uint8_t* d_images, uint16_t* d_labels,
+                    float* d_weights, anh_crop_pick* picks) {
+        ANH_REQUIRE(classes >= 1 && classes <= kCropMaxClasses, "crop batch: class count must be 1..64");
+        const Staged g = stage_specs(specs, draws, n, dim);
+        const hipStream_t st = stream.get();
         launch_crop_pixels(d_specs.as<CropSource>(), n, dim, channels, d_images, d_labels, d_hist.as<unsigned>(), d_first.as<unsigned>(), d_bad.as<int>(), classes, st);
-        HIP_CHECK(hipMemcpyAsync(h_hist, d_hist.p, tab, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(h_first, d_first.p, tab, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(h_bad, d_bad.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(g.h_hist, d_hist.p, g.tab, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(g.h_first, d_first.p, g.tab, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(g.h_bad, d_bad.p, 8, hipMemcpyDeviceToHost, st));
+        if (draws && picks) HIP_CHECK(hipMemcpyAsync(g.h_picks, d_picks.p, (size_t)n * sizeof(DatasetPick), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        ANH_REQUIRE(*h_bad == 0, "label value exceeds the class count");
+        ANH_REQUIRE(g.h_bad[1] == 0, "picked crops: the point index does not match the resident labels");
+        ANH_REQUIRE(g.h_bad[0] == 0, "label value exceeds the class count");
+        if (draws && picks) picks_to_host(g, g.h_jobs, n, picks);
         for (int i = 0; i < n; ++i)
-            set_weights_table(h_hist + (size_t)i * kCropMaxClasses, h_first + (size_t)i * kCropMaxClasses, kCropMaxClasses, (long long)dim * dim, cw, iw,
-                              h_table + (size_t)i * kCropMaxClasses);
-        HIP_CHECK(hipMemcpyAsync(d_table.p, h_table, tab, hipMemcpyHostToDevice, st));
+            set_weights_table(g.h_hist + (size_t)i * kCropMaxClasses, g.h_first + (size_t)i * kCropMaxClasses, kCropMaxClasses, (long long)dim * dim, cw, iw,
+                              g.h_table + (size_t)i * kCropMaxClasses);
+        HIP_CHECK(hipMemcpyAsync(d_table.p, g.h_table, g.tab, hipMemcpyHostToDevice, st));
         launch_crop_weights(d_labels, d_table.as<float>(), n, dim, d_weights, st);
     }
 };
@@ -1946,6 +1994,7 @@ int anh_dataset_remove(anh_dataset* d, int index) {
         ANH_REQUIRE(index >= 0 && (size_t)index < d->items.size() && d->items[(size_t)index].height > 0, "dataset remove: no such image");
         HIP_CHECK(hipStreamSynchronize(d->stream.get()));   // the crop kernels that read the image have finished
         anh_dataset::Item& it = d->items[(size_t)index];
+        d->drop_index(it);
         d->resident_bytes -= (uint64_t)it.height * it.width * (d->channels + 2);
         it.image.release(); it.labels.release(); it.height = it.width = 0;
         d->free_slots.push_back(index);
@@ -1954,53 +2003,170 @@ int anh_dataset_remove(anh_dataset* d, int index) {
 int anh_dataset_resident_bytes(const anh_dataset* d, uint64_t* bytes) {
     return guarded([&] { ANH_REQUIRE(d && bytes, "null argument"); *bytes = d->resident_bytes; });
 }
+int anh_dataset_prepare(anh_dataset* d, int index, const uint16_t* classes_to_ignore, int n_ignore, double by_area, double by_width, double by_height,
+                        int receptive_field_side, anh_dataset_info* info) {
+    return guarded([&] {
+        ANH_REQUIRE(d && info, "null argument");
+        ANH_REQUIRE(n_ignore >= 0 && n_ignore <= 64 && (classes_to_ignore || n_ignore == 0), "dataset prepare: 0..64 classes to ignore");
+        ANH_REQUIRE(receptive_field_side > 0, "dataset prepare: the receptive-field side must be positive");
+        ANH_REQUIRE(!(by_area < 0) && !(by_width < 0) && !(by_height < 0) && by_area == by_area && by_width == by_width && by_height == by_height,
+                    "dataset prepare: negative threshold");
+        anh_dataset::Item& it = d->item(index, "dataset prepare");
+        const hipStream_t st = d->stream.get();
+        HIP_CHECK(hipStreamSynchronize(st));   // the crop kernels that read the labels have finished
+        d->drop_index(it);
+        const int H = it.height, W = it.width;
+        const int64_t pixels = (int64_t)H * W;
+        const size_t blocks = dataset_index_blocks(pixels);
+        const bool by_size = std::isfinite(by_area) || std::isfinite(by_width) || std::isfinite(by_height);
+        // words: [0] pixels relabelled by class, [1] by size, [2] the one table's row offset (0), [3..67) class totals, [67] bad label | blob count
+        constexpr size_t kWords = 3 + kCropMaxClasses + 1;
+        d->prep_words.reserve(kWords * 8); d->prep_counts.reserve((size_t)kCropMaxClasses * blocks * 4);
+        if (kWords * 8 > d->pinned.bytes) d->pinned.reserve(kWords * 8);
+        if (by_size) {
+            d->blob_parent.reserve((size_t)pixels * 4); d->blob_map.reserve((size_t)pixels * 4); d->blob_sums.reserve(blob_scan_blocks(pixels) * 4);
+        }
+        unsigned long long* words = d->prep_words.as<unsigned long long>();
+        unsigned long long* h_words = d->pinned.as<unsigned long long>();
+        int* bad = reinterpret_cast<int*>(words + 3 + kCropMaxClasses);
+        unsigned* blob_count = reinterpret_cast<unsigned*>(bad + 1);
+        uint16_t* labels = it.labels.as<uint16_t>();
+        HIP_CHECK(hipMemsetAsync(words, 0, kWords * 8, st));
+        if (n_ignore > 0) {
+            DatasetIgnoreList list{};
+            list.n = n_ignore;
+            for (int i = 0; i < n_ignore; ++i) list.values[i] = classes_to_ignore[i];
+            launch_dataset_relabel(labels, pixels, list, words, st);
+        }
+        if (by_size) {
+            launch_blob_label(labels, 1, H, W, d->blob_parent.as<int>(), d->blob_map.as<uint32_t>(), d->blob_sums.as<unsigned>(), blob_count, st);
+            HIP_CHECK(hipMemcpyAsync(h_words, blob_count, 4, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            const uint32_t rows = *reinterpret_cast<const unsigned*>(h_words) - 1u;   // "labels including the background one"
+            d->blob_table.reserve(((size_t)rows + 1) * sizeof(anh_region));   // the labelling does not need the table: sized once the count is back
+            const double rf = (double)receptive_field_side;
+            launch_blob_number(d->blob_parent.as<int>(), d->blob_map.as<uint32_t>(), labels, 1, H, W, d->blob_table.as<anh_region>(), words + 2, st);
+            launch_dataset_ignore_large(labels, d->blob_map.as<uint32_t>(), d->blob_table.as<anh_region>(), rows, H, W, by_area * rf * rf, by_width * rf, by_height * rf,
+                                        words + 1, st);
+        }
+        launch_dataset_index(labels, pixels, d->prep_counts.as<unsigned>(), words + 3, bad, st);
+        HIP_CHECK(hipMemcpyAsync(h_words, words, kWords * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        anh_dataset_info got{};
+        got.ignored_by_class = (int64_t)h_words[0]; got.ignored_by_size = (int64_t)h_words[1];
+        ANH_REQUIRE(*reinterpret_cast<const int*>(h_words + 3 + kCropMaxClasses) == 0, "dataset prepare: a label value is 64 or more (and not the ignore label)");
+        for (int c = 0; c < kCropMaxClasses; ++c)
+            if (h_words[3 + c]) { got.classes[got.present] = (uint16_t)c; got.counts[got.present] = h_words[3 + c]; ++got.present; }
+        if (got.present) {
+            it.index.reserve((size_t)got.present * blocks * 4);
+            for (int i = 0; i < got.present; ++i)
+                HIP_CHECK(hipMemcpyAsync(it.index.as<unsigned>() + (size_t)i * blocks, d->prep_counts.as<unsigned>() + (size_t)got.classes[i] * blocks, blocks * 4,
+                                         hipMemcpyDeviceToDevice, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
+        it.index_bytes = (uint64_t)got.present * blocks * 4;
+        d->resident_bytes += it.index_bytes;
+        it.info = got; it.prepared = true;
+        *info = got;
+    });
+}
+int anh_dataset_scratch_bytes(const anh_dataset* d, uint64_t* bytes) {
+    return guarded([&] {
+        ANH_REQUIRE(d && bytes, "null argument");
+        *bytes = d->prep_counts.bytes + d->prep_words.bytes + d->blob_parent.bytes + d->blob_map.bytes + d->blob_sums.bytes + d->blob_table.bytes;
+    });
+}
+int anh_dataset_labels(anh_dataset* d, int index, uint16_t* labels) {
+    return guarded([&] {
+        ANH_REQUIRE(d && labels, "null argument");
+        const anh_dataset::Item& it = d->item(index, "dataset labels");
+        HIP_CHECK(hipStreamSynchronize(d->stream.get()));
+        HIP_CHECK(hipMemcpy(labels, it.labels.p, (size_t)it.height * it.width * 2, hipMemcpyDeviceToHost));
+    });
+}
+int anh_resolve_pick(const anh_dataset_info* info, uint32_t class_draw, uint64_t point_draw, uint16_t* label, uint64_t* k) {
+    return guarded([&] { ANH_REQUIRE(info && label && k, "null argument"); resolve_pick(*info, class_draw, point_draw, label, k); });
+}
+int anh_dataset_pick(anh_dataset* d, const anh_crop_spec* specs, const anh_crop_draw* draws, int n, int dim, anh_crop_pick* out) {
+    return guarded([&] {
+        ANH_REQUIRE(d && specs && draws && out, "null argument");
+        const anh_dataset::Staged g = d->stage_specs(specs, draws, n, dim);
+        const hipStream_t st = d->stream.get();
+        HIP_CHECK(hipMemcpyAsync(g.h_bad, d->d_bad.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(g.h_picks, d->d_picks.p, (size_t)n * sizeof(DatasetPick), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        ANH_REQUIRE(g.h_bad[1] == 0, "picked crops: the point index does not match the resident labels");
+        anh_dataset::picks_to_host(g, g.h_jobs, n, out);
+    });
+}
+namespace {
+void crop_batch_to_host(anh_dataset* d, const anh_crop_spec* specs, const anh_crop_draw* draws, int n, int dim, int classes, double class_weight, double image_weight,
+                        uint8_t* images, anh_wlabel* labels, anh_crop_pick* picks) {
+    ANH_REQUIRE(d && specs && images && labels && n >= 1 && dim >= 1, "crop batch: bad argument");
+    const size_t plane = (size_t)dim * dim;
+    const BatchLayout lay((size_t)n, plane, d->channels);
+    const hipStream_t stream = d->stream.get();
+    d->out.reserve(lay.total);
+    uint8_t* base = d->out.as<uint8_t>();
+    d->crop_batch(specs, draws, n, dim, classes, class_weight, image_weight, base, lay.labels(base), lay.weights(base), picks);
+    std::vector<uint16_t> hl((size_t)n * plane);
+    std::vector<float> hw((size_t)n * plane);
+    HIP_CHECK(hipMemcpyAsync(images, base, lay.img_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(hl.data(), lay.labels(base), hl.size() * 2, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(hw.data(), lay.weights(base), hw.size() * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (size_t i = 0; i < hl.size(); ++i) { labels[i].label = hl[i]; labels[i].weight = hw[i]; }
+}
+// the crops of step k are cut on the dataset's stream while the trainer's stream still runs step k-1
+void step_on_crops(anh_trainer* h, anh_dataset* d, const anh_crop_spec* specs, const anh_crop_draw* draws, int n, int dim, double class_weight, double image_weight) {
+    ANH_REQUIRE(n >= 1 && dim >= 1, "empty mini-batch");
+    ANH_REQUIRE(h->reps.size() == 1, "device-cut crops live on ONE device: a handle over several devices takes host mini-batches (anh_trainer_step)");
+    Engine& e = h->engine();
+    const int C = e.spec.cfg.in_channels, K = e.spec.cfg.classes;
+    ANH_REQUIRE(C == d->channels, "the dataset's channel count differs from the net's");
+    const BatchLayout lay((size_t)n, (size_t)dim * dim, C);
+    anh_trainer::StageSet& st = h->stage[0][h->host_steps & 1];
+    const hipEvent_t uploaded = st.uploaded.ensure(), consumed = st.consumed.ensure();
+    if (lay.total > st.dev.bytes) {
+        if (st.in_flight) wait_event(consumed, h->reps.size() > 1);
+        st.dev.reserve(lay.total);
+    }
+    if (st.in_flight) HIP_CHECK(hipStreamWaitEvent(d->stream.get(), consumed, 0));
+    uint8_t* dbase = st.dev.as<uint8_t>();
+    d->crop_batch(specs, draws, n, dim, K, class_weight, image_weight, dbase, lay.labels(dbase), lay.weights(dbase), nullptr);
+    HIP_CHECK(hipEventRecord(uploaded, d->stream.get()));
+    HIP_CHECK(hipStreamWaitEvent(e.stream, uploaded, 0));
+    int rc = anh_trainer_forward_backward_device(h, dbase, lay.labels(dbase), lay.weights(dbase), n, dim, dim, (double)n);
+    if (rc != ANH_OK) fail(rc, g_error);
+    rc = anh_trainer_apply_update(h, 1.0);
+    if (rc != ANH_OK) fail(rc, g_error);
+    HIP_CHECK(hipEventRecord(consumed, e.stream));
+    st.in_flight = true;
+    ++h->host_steps;
+}
+}  // namespace
 int anh_dataset_crop_batch(anh_dataset* d, const anh_crop_spec* specs, int n, int dim, int classes, double class_weight, double image_weight,
                            uint8_t* images, anh_wlabel* labels) {
+    return guarded([&] { crop_batch_to_host(d, specs, nullptr, n, dim, classes, class_weight, image_weight, images, labels, nullptr); });
+}
+int anh_dataset_crop_batch_picked(anh_dataset* d, const anh_crop_spec* specs, const anh_crop_draw* draws, int n, int dim, int classes, double class_weight,
+                                  double image_weight, uint8_t* images, anh_wlabel* labels, anh_crop_pick* picks) {
     return guarded([&] {
-        ANH_REQUIRE(d && specs && images && labels && n >= 1 && dim >= 1, "crop batch: bad argument");
-        const size_t plane = (size_t)dim * dim;
-        const BatchLayout lay((size_t)n, plane, d->channels);
-        const hipStream_t stream = d->stream.get();
-        d->out.reserve(lay.total);
-        uint8_t* base = d->out.as<uint8_t>();
-        d->crop_batch(specs, n, dim, classes, class_weight, image_weight, base, lay.labels(base), lay.weights(base));
-        std::vector<uint16_t> hl((size_t)n * plane);
-        std::vector<float> hw((size_t)n * plane);
-        HIP_CHECK(hipMemcpyAsync(images, base, lay.img_bytes, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipMemcpyAsync(hl.data(), lay.labels(base), hl.size() * 2, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipMemcpyAsync(hw.data(), lay.weights(base), hw.size() * 4, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        for (size_t i = 0; i < hl.size(); ++i) { labels[i].label = hl[i]; labels[i].weight = hw[i]; }
+        ANH_REQUIRE(draws, "null argument");
+        crop_batch_to_host(d, specs, draws, n, dim, classes, class_weight, image_weight, images, labels, picks);
     });
 }
 int anh_trainer_step_crops(anh_trainer* h, anh_dataset* d, const anh_crop_spec* specs, int n, int dim, double class_weight, double image_weight) {
     return guarded([&] {
         ANH_REQUIRE(h && d && specs, "null argument");
-        ANH_REQUIRE(n >= 1 && dim >= 1, "empty mini-batch");
-        ANH_REQUIRE(h->reps.size() == 1, "device-cut crops live on ONE device: a handle over several devices takes host mini-batches (anh_trainer_step)");
-        Engine& e = h->engine();
-        const int C = e.spec.cfg.in_channels, K = e.spec.cfg.classes;
-        ANH_REQUIRE(C == d->channels, "the dataset's channel count differs from the net's");
-        const BatchLayout lay((size_t)n, (size_t)dim * dim, C);
-        anh_trainer::StageSet& st = h->stage[0][h->host_steps & 1];
-        const hipEvent_t uploaded = st.uploaded.ensure(), consumed = st.consumed.ensure();
-        if (lay.total > st.dev.bytes) {
-            if (st.in_flight) wait_event(consumed, h->reps.size() > 1);
-            st.dev.reserve(lay.total);
-        }
-        // the crops of step k are cut on the dataset's stream while the trainer's stream still runs step k-1
-        if (st.in_flight) HIP_CHECK(hipStreamWaitEvent(d->stream.get(), consumed, 0));
-        uint8_t* dbase = st.dev.as<uint8_t>();
-        d->crop_batch(specs, n, dim, K, class_weight, image_weight, dbase, lay.labels(dbase), lay.weights(dbase));
-        HIP_CHECK(hipEventRecord(uploaded, d->stream.get()));
-        HIP_CHECK(hipStreamWaitEvent(e.stream, uploaded, 0));
-        int rc = anh_trainer_forward_backward_device(h, dbase, lay.labels(dbase), lay.weights(dbase), n, dim, dim, (double)n);
-        if (rc != ANH_OK) fail(rc, g_error);
-        rc = anh_trainer_apply_update(h, 1.0);
-        if (rc != ANH_OK) fail(rc, g_error);
-        HIP_CHECK(hipEventRecord(consumed, e.stream));
-        st.in_flight = true;
-        ++h->host_steps;
+        step_on_crops(h, d, specs, nullptr, n, dim, class_weight, image_weight);
+    });
+}
+int anh_trainer_step_crops_picked(anh_trainer* h, anh_dataset* d, const anh_crop_spec* specs, const anh_crop_draw* draws, int n, int dim, double class_weight,
+                                  double image_weight) {
+    return guarded([&] {
+        ANH_REQUIRE(h && d && specs && draws, "null argument");
+        step_on_crops(h, d, specs, draws, n, dim, class_weight, image_weight);
     });
 }
 int anh_ignore_large_nonzero_regions(uint16_t* labels, int nr, int nc, double by_area, double by_width, double by_height, int rf, int64_t* ignored) {

@@ -170,6 +170,17 @@ anh_rect random_rect_containing_point(uint32_t draw_x, uint32_t draw_y, long px,
     return r;
 }
 
+// which labelled point a crop is centred on (annonet_train_main.cpp:121,131): a class, uniform over the present ones, then a point of it.
+// The classes are taken in ascending value (the reference walks an unordered_map, whose order is implementation-defined).
+int resolve_pick(const anh_dataset_info& info, uint32_t class_draw, uint64_t point_draw, uint16_t* label, uint64_t* k) {
+    ANH_REQUIRE(info.present >= 1 && info.present <= 64, "resolve pick: no labelled class to draw from");
+    const int slot = (int)(class_draw % (uint32_t)info.present);
+    ANH_REQUIRE(info.counts[slot] >= 1, "resolve pick: a present class without pixels");
+    *label = info.classes[slot];
+    *k = point_draw % info.counts[slot];
+    return slot;
+}
+
 // outpaint (annonet.h:74-120): every pixel outside `inside` takes the value of the nearest pixel of `inside`.
 void outpaint(uint8_t* image, int nr, int nc, int channels, anh_rect in) {
     in.left = std::max(in.left, 0L); in.top = std::max(in.top, 0L);

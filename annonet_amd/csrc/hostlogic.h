@@ -16,6 +16,8 @@ void set_weights(const uint16_t* labels, int nr, int nc, double class_weight, do
 void set_weights_table(const unsigned* counts, const unsigned* first_position, int n_labels, long long pixels, double class_weight,
                        double image_weight, float* table);
 anh_rect random_rect_containing_point(uint32_t draw_x, uint32_t draw_y, long px, long py, long w, long h);
+// -> the slot of info.classes the class draw lands on
+int resolve_pick(const anh_dataset_info& info, uint32_t class_draw, uint64_t point_draw, uint16_t* label, uint64_t* k);
 void outpaint(uint8_t* image, int nr, int nc, int channels, anh_rect inside);
 int64_t count_steps_without_decrease(const double* values, int64_t n, double probability_of_decrease);
 // annonet.dnn envelope: dlib serialize framing of (string classes_json, double downscaling_factor, string serialized_net)

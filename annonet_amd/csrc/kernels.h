@@ -335,6 +335,34 @@ void launch_blob_stats(const uint32_t* d_blobs, const uint16_t* d_labels, const 
 // labels[p] = 0 where p's blob has no seed: one launch
 void launch_blob_filter(uint16_t* d_labels, const uint32_t* d_blobs, const anh_region* d_table, const unsigned long long* d_row_offsets, int n, int64_t pixels,
                         hipStream_t s);
+// ---- dataset preparation and crop-centre sampling (kernels_dataset.hip; annonet_train_main.cpp:414-502, :121-131) ----
+constexpr int kDatasetIndexPixels = 1024;   // pixels per block of the point index
+size_t dataset_index_blocks(int64_t pixels);
+struct DatasetIgnoreList { uint16_t values[64]; int n; };
+// labels equal to one of list.values become ANH_LABEL_IGNORE; *d_changed += the pixels changed
+void launch_dataset_relabel(uint16_t* d_labels, int64_t pixels, const DatasetIgnoreList& list, unsigned long long* d_changed, hipStream_t s);
+// d_blobs, d_table: what launch_blob_label + launch_blob_number (n = 1, with a table) left for this label map, `rows` blobs.  Area and
+// bounding box of every blob go into its row (launch_blob_stats is not involved: no planes, no seed flags); then every pixel of a blob with
+// (double)area > max_points, (double)width > max_width or (double)height > max_height becomes ANH_LABEL_IGNORE.  *d_changed += the pixels
+// changed that were not ANH_LABEL_IGNORE before.
+void launch_dataset_ignore_large(uint16_t* d_labels, const uint32_t* d_blobs, anh_region* d_table, uint32_t rows, int h, int w, double max_points, double max_width,
+                                 double max_height, unsigned long long* d_changed, hipStream_t s);
+// d_counts [kCropMaxClasses][dataset_index_blocks(pixels)]: afterwards row c holds, per block of 1024 pixels in raster order, the number of
+// pixels of class c in the blocks before it; d_totals[c] = the pixels of class c; *d_bad = 1 (else untouched) where a label is >=
+// kCropMaxClasses and not ANH_LABEL_IGNORE
+void launch_dataset_index(const uint16_t* d_labels, int64_t pixels, unsigned* d_counts, unsigned long long* d_totals, int* d_bad, hipStream_t s);
+struct DatasetPickJob {
+    const uint16_t* labels; const unsigned* prefix;   // the image's label map and the index row of `label`
+    long long pixels; int width, blocks;
+    unsigned k;                                       // the k-th pixel of `label` in raster order, k < the class's total
+    unsigned draw_x, draw_y;                          // random_rect_containing_point's two draws
+    int src_dim;                                      // side of the rectangle, round(dim * further_downscaling_factor)
+    uint16_t label;
+};
+struct DatasetPick { int x, y, left, top; };
+// one wave per pick: d_picks[i] = the pixel and the rectangle's corner; d_specs[i].left / .top receive the corner (launch_crop_pixels reads
+// them next); *d_failed = 1 (else untouched) where the index and the labels disagree
+void launch_dataset_pick(const DatasetPickJob* d_jobs, int n, CropSource* d_specs, DatasetPick* d_picks, int* d_failed, hipStream_t s);
 // ---- scoring result maps against their ground truth (kernels_score.hip; annonet_infer_main.cpp:482-491, :202-272) ----
 // d_maps [2n][h][w] = [n truth maps ; n result maps] and d_blobs their blob maps (launch_blob_label + launch_blob_number);
 // d_row_offsets: 2n values, the first vote row of every map (the host's exclusive sum of the labeller's counts: blobs + 1 = regions);

@@ -24,6 +24,7 @@
 
 #include <climits>
 
+#include "blockscan.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -163,30 +164,6 @@ __global__ __launch_bounds__(128) void blob_seam_kernel(const uint16_t* labels, 
         if (nx / T == tile_x && ny / T == tile_y) continue;   // the local pass has joined these
         if (labels[(size_t)ny * w + nx] == l) global_unite(parent, p, ny * w + nx);
     }
-}
-
-// block-wide exclusive prefix sum over THREADS values; *total = their sum.  Every thread of the block calls it.
-template <int THREADS>
-__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* wave_sums, unsigned* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned up = __shfl_up(x, d, 64);
-        if (lane >= d) x += up;
-    }
-    __syncthreads();   // a previous call's readers are done with wave_sums
-    if (lane == 63) wave_sums[wave] = x;
-    __syncthreads();
-    unsigned before = 0, all = 0;
-#pragma unroll
-    for (int i = 0; i < THREADS / 64; ++i) {
-        const unsigned s = wave_sums[i];
-        if (i < wave) before += s;
-        all += s;
-    }
-    *total = all;
-    return before + x - v;
 }
 
 // roots[p] = root(p) + 1 (0: background); sums[block] = number of roots among the block's 1024 pixels.

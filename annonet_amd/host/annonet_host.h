@@ -181,14 +181,17 @@ inline uint16_t rgba_label_to_index_label(const dlib::rgb_alpha_pixel& rgba_labe
     throw std::runtime_error(error.str());
 }
 
-inline void decode_rgba_label_image(const dlib::matrix<dlib::rgb_alpha_pixel>& rgba_label_image, sample_type& ground_truth_sample, const std::vector<AnnoClass>& anno_classes) {   // annonet.cpp:41-58
+// build_point_lists = false (the training tool with --device-sampling: the library indexes the resident label image instead): the label
+// image alone, no labeled_points_by_class
+inline void decode_rgba_label_image(const dlib::matrix<dlib::rgb_alpha_pixel>& rgba_label_image, sample_type& ground_truth_sample, const std::vector<AnnoClass>& anno_classes,
+                                    bool build_point_lists = true) {   // annonet.cpp:41-58
     const long nr = rgba_label_image.nr(), nc = rgba_label_image.nc();
     ground_truth_sample.label_image.set_size(nr, nc);
     ground_truth_sample.labeled_points_by_class.clear();
     for (long r = 0; r < nr; ++r)
         for (long c = 0; c < nc; ++c) {
             const uint16_t label = rgba_label_to_index_label(rgba_label_image(r, c), anno_classes);
-            if (label != dlib::loss_multiclass_log_per_pixel_::label_to_ignore) ground_truth_sample.labeled_points_by_class[label].push_back(dlib::point(c, r));
+            if (build_point_lists && label != dlib::loss_multiclass_log_per_pixel_::label_to_ignore) ground_truth_sample.labeled_points_by_class[label].push_back(dlib::point(c, r));
             ground_truth_sample.label_image(r, c) = label;
         }
 }
@@ -315,7 +318,7 @@ inline void save_png(const dlib::matrix<dlib::rgb_alpha_pixel>& image, const std
 // resize_input_image = false (the inference program when annonet_infer_scaled shrinks the image on the GPU): the image stays at its
 // original size; the ground truth is still brought to the size the shrunk image WOULD have (anh_scaled_dims), where it is scored.
 inline sample_type read_sample(const image_filenames_type& image_filenames, const std::vector<AnnoClass>& anno_classes, bool require_ground_truth, double downscaling_factor,
-                               bool resize_input_image = true) {   // annonet.cpp:143-176
+                               bool resize_input_image = true, bool build_point_lists = true) {   // annonet.cpp:143-176
     sample_type sample;
     sample.image_filenames = image_filenames;
     try {
@@ -333,7 +336,7 @@ inline sample_type read_sample(const image_filenames_type& image_filenames, cons
             if (rgba_label_image.nr() != sample.original_height || rgba_label_image.nc() != sample.original_width) sample.error = "Label image size mismatch";
             else {
                 resize_label_image(rgba_label_image, scaled_width, scaled_height);
-                decode_rgba_label_image(rgba_label_image, sample, anno_classes);
+                decode_rgba_label_image(rgba_label_image, sample, anno_classes, build_point_lists);
             }
         } else if (require_ground_truth) sample.error = "No ground truth available";
     } catch (std::exception& e) { sample.error = e.what(); }

@@ -42,6 +42,8 @@ struct crop {   // annonet_train_main.cpp:58-69
     // device path: the crop is NOT cut here; the spec travels to the GPU instead (dataset_index = the full image's number in the HBM-resident dataset)
     anh_crop_spec spec{};
     bool is_spec = false;
+    anh_crop_draw draw{};      // is_picked: the rectangle is not in the spec; these draws pick it on the device
+    bool is_picked = false;
 };
 
 struct augmentation_options {   // the reference reads these from cxxopts in randomly_crop_image (:124,178,184-185,196-197,218,227)
@@ -84,15 +86,8 @@ inline dlib::rectangle random_rect_containing_point(host_rand& rnd, const dlib::
 
 // The random decisions of randomly_crop_image (:110-232) in the reference's order, without touching pixels: which labelled point,
 // the rectangle around it, flips, brightness factor, noise level (+ a seed for the device's counter-based draws), colour offsets.
-inline anh_crop_spec draw_crop_spec(int dim, const sample_type& full_sample, int dataset_index, host_rand& rnd, const augmentation_options& o) {
-    const size_t class_index = rnd.get_random_32bit_number() % full_sample.labeled_points_by_class.size();
-    auto i = full_sample.labeled_points_by_class.begin();
-    std::advance(i, (long)class_index);
-    const size_t point_index = rnd.get_random_64bit_number() % i->second.size();
-    const int dim_before_downscaling = (int)std::round(dim * o.further_downscaling_factor);
-    const dlib::rectangle rect = random_rect_containing_point(rnd, i->second[point_index], dim_before_downscaling, dim_before_downscaling);
-    anh_crop_spec s{};
-    s.image = dataset_index; s.left = rect.left(); s.top = rect.top();
+// draw_crop_augmentations: everything behind the rectangle (:183-231).
+inline void draw_crop_augmentations(anh_crop_spec& s, host_rand& rnd, const augmentation_options& o) {
     s.further_downscaling_factor = o.further_downscaling_factor;
     s.flip_left_right = o.allow_flip_left_right && rnd.get_random_double() > 0.5;
     s.flip_upside_down = o.allow_flip_upside_down && rnd.get_random_double() > 0.5;
@@ -104,6 +99,29 @@ inline anh_crop_spec draw_crop_spec(int dim, const sample_type& full_sample, int
         s.noise_seed = rnd.get_random_64bit_number();
     }
     if (o.allow_random_color_offset && NetPimpl::kInputChannels == 3) draw_color_offset(rnd, s.color_offset);
+}
+inline anh_crop_spec draw_crop_spec(int dim, const sample_type& full_sample, int dataset_index, host_rand& rnd, const augmentation_options& o) {
+    const size_t class_index = rnd.get_random_32bit_number() % full_sample.labeled_points_by_class.size();
+    auto i = full_sample.labeled_points_by_class.begin();
+    std::advance(i, (long)class_index);
+    const size_t point_index = rnd.get_random_64bit_number() % i->second.size();
+    const int dim_before_downscaling = (int)std::round(dim * o.further_downscaling_factor);
+    const dlib::rectangle rect = random_rect_containing_point(rnd, i->second[point_index], dim_before_downscaling, dim_before_downscaling);
+    anh_crop_spec s{};
+    s.image = dataset_index; s.left = rect.left(); s.top = rect.top();
+    draw_crop_augmentations(s, rnd, o);
+    return s;
+}
+// The same draws in the same order for a crop whose centre is picked ON THE DEVICE (anh_dataset_prepare's index of the resident label
+// image): the class, the point and the rectangle's two draws travel as numbers (anh_crop_draw); no point list is consulted.
+inline anh_crop_spec draw_picked_crop_spec(host_rand& rnd, const augmentation_options& o, anh_crop_draw& draw) {
+    draw.class_draw = rnd.get_random_32bit_number();
+    draw.point_draw = rnd.get_random_64bit_number();
+    draw.rect_draw_x = rnd.get_random_32bit_number();
+    draw.rect_draw_y = rnd.get_random_32bit_number();
+    anh_crop_spec s{};
+    s.image = -1;
+    draw_crop_augmentations(s, rnd, o);
     return s;
 }
 
@@ -182,6 +200,16 @@ inline void randomly_crop_image(int dim, const sample_type& full_sample, crop& c
 }
 
 // ---------------------------------------------------------------------------------------- per-image preparation
+// labeled_points_by_class from the label image, in raster order: what decode_rgba_label_image (annonet.cpp:41-58) leaves
+inline void build_labeled_points(sample_type& sample) {
+    sample.labeled_points_by_class.clear();
+    for (long r = 0; r < sample.label_image.nr(); ++r)
+        for (long c = 0; c < sample.label_image.nc(); ++c) {
+            const uint16_t label = sample.label_image(r, c);
+            if (label != dlib::loss_multiclass_log_per_pixel_::label_to_ignore) sample.labeled_points_by_class[label].push_back(dlib::point(c, r));
+        }
+}
+
 inline void ignore_classes_to_ignore(sample_type& sample, const std::vector<uint16_t>& classes_to_ignore) {   // :414-424
     for (const auto class_to_ignore : classes_to_ignore) {
         const auto i = sample.labeled_points_by_class.find(class_to_ignore);
@@ -199,13 +227,7 @@ inline void ignore_large_nonzero_regions(sample_type& sample, double by_area, do
     int64_t ignored = 0;
     NetPimpl::check(anh_ignore_large_nonzero_regions(&*sample.label_image.begin(), (int)sample.label_image.nr(), (int)sample.label_image.nc(), by_area, by_width, by_height,
                                                      NetPimpl::TrainingNet::GetRequiredInputDimension(), &ignored));
-    if (!ignored) return;
-    sample.labeled_points_by_class.clear();
-    for (long r = 0; r < sample.label_image.nr(); ++r)
-        for (long c = 0; c < sample.label_image.nc(); ++c) {
-            const uint16_t label = sample.label_image(r, c);
-            if (label != dlib::loss_multiclass_log_per_pixel_::label_to_ignore) sample.labeled_points_by_class[label].push_back(dlib::point(c, r));
-        }
+    if (ignored) build_labeled_points(sample);
 }
 
 // ---------------------------------------------------------------------------------------- LRU cache of full images

@@ -8,8 +8,9 @@
 // schedule constants (:388-390), the stop rule (:569-577), annonet.dnn written at step 0, every save-interval steps and at the end
 // (:557-565,611-613,634-636), the trainer state file name, exit codes (2: option / in-loop errors, 1: everything else).
 // What differs: by default the loader threads push crop SPECS and the mini-batch is cut on the device from full
-// images resident in HBM; --host-crops cuts crops on the loader threads as the reference does; --devices trains data-parallel from
-// this one process; the large-region filter the reference parses but never calls is applied when asked for.
+// images resident in HBM; --host-crops cuts crops on the loader threads as the reference does; --device-sampling leaves the two label
+// filters and the choice of every crop's centre to the device as well (no labelled-point lists on the host); --devices trains
+// data-parallel from this one process; the large-region filter the reference parses but never calls is applied when asked for.
 #define ANNONET_HIP_NO_DLIB
 #include "annonet_train_host.h"
 
@@ -25,7 +26,7 @@ struct TrainSettings {
     std::string directory, precision = "bf16";
     double hbm_budget_gib = 64.0;   // full images kept resident in HBM on the device-crop path (LRU beyond it)
     double initial_downscaling = 1.0, further_downscaling = 1.0;
-    bool flip_ud = false, flip_lr = false, color_offset = false, quiet_empty_labels = false, host_crops = false;
+    bool flip_ud = false, flip_lr = false, color_offset = false, quiet_empty_labels = false, host_crops = false, device_sampling = false;
     double brightness_probability = 0.0, brightness_sigma = 0.1, noise_stddev = 0.0, class_weight = 0.5, image_weight = 0.5;
     std::vector<uint16_t> ignored_classes;
     double region_area = std::numeric_limits<double>::infinity(), region_width = std::numeric_limits<double>::infinity(), region_height = std::numeric_limits<double>::infinity();
@@ -50,7 +51,7 @@ const char* usage_text() {
            "      --initial-learning-rate arg   --learning-rate-shrink-factor arg   --min-learning-rate arg   --save-interval arg\n"
            "  -t, --relative-training-length arg   --max-total-steps arg   -c, --cached-image-count arg   --data-loader-thread-count arg\n"
            "      --no-empty-label-image-warning   --primary-cuda-device arg\n"
-           "  extensions: --host-crops   --devices 0,1,...   --precision bf16|fp32   --seed arg   --hbm-image-budget-gib arg\n"
+           "  extensions: --host-crops   --device-sampling   --devices 0,1,...   --precision bf16|fp32   --seed arg   --hbm-image-budget-gib arg\n"
            "      --validation-directory arg   --validation-interval arg (default: the save interval)   --validation-precision bf16|fp32\n";
 }
 
@@ -89,6 +90,7 @@ TrainSettings read_command_line(int argc, char** argv) {
     std::map<std::string, bool*> switches = {
         {"--allow-flip-upside-down", &s.flip_ud}, {"-u", &s.flip_ud}, {"--allow-flip-left-right", &s.flip_lr}, {"-l", &s.flip_lr},
         {"--allow-random-color-offset", &s.color_offset}, {"-o", &s.color_offset}, {"--no-empty-label-image-warning", &s.quiet_empty_labels}, {"--host-crops", &s.host_crops},
+        {"--device-sampling", &s.device_sampling},
     };
     for (int i = 1; i < argc; ++i) {
         const std::string word = argv[i];
@@ -105,6 +107,8 @@ TrainSettings read_command_line(int argc, char** argv) {
     if (s.validation_precision.empty()) s.validation_precision = s.precision;
     if (s.validation_precision != "bf16" && s.validation_precision != "fp32") throw std::runtime_error("--validation-precision must be fp32 or bf16");
     if (s.validation_interval == 0) s.validation_interval = s.save_interval;
+    if (s.device_sampling && (s.host_crops || s.devices.size() > 1))
+        throw std::runtime_error("--device-sampling draws crop centres from the images resident on ONE device: it excludes --host-crops and several --devices");
     return s;
 }
 
@@ -141,6 +145,9 @@ class CropFeeder {
         if (!queue_.dequeue(item)) throw std::runtime_error("the loader threads stopped");
         return item;
     }
+    // what the loader threads spent per decoded image on the point lists and the two filters (--device-sampling: nothing, the main
+    // thread's Dataset::Prepare does that work)
+    double preparation_ms_mean() const { const uint64_t n = prepared_; return n ? 1e-6 * (double)prepare_ns_ / (double)n : 0.0; }
     std::string statistics(size_t resident) const {
         std::ostringstream o;
         o << "full images decoded: " << cache_.misses() << ", cache hits: " << cache_.hits() << ", evictions: " << cache_.evictions() << ", images resident in HBM: " << resident;
@@ -149,11 +156,15 @@ class CropFeeder {
 
   private:
     std::shared_ptr<sample_type> decode(const image_filenames_type& names, const std::vector<AnnoClass>& classes) {   // :504-510 (+ the filters of :414-502)
-        auto sample = std::make_shared<sample_type>(read_sample(names, classes, true, settings_.initial_downscaling));
-        if (sample->error.empty()) {
+        auto sample = std::make_shared<sample_type>(read_sample(names, classes, true, settings_.initial_downscaling, true, false));
+        if (sample->error.empty() && !settings_.device_sampling) {
+            const auto t0 = std::chrono::steady_clock::now();
+            build_labeled_points(*sample);   // the lists decode_rgba_label_image builds, apart from the decoding so that their cost can be told
             ignore_classes_to_ignore(*sample, settings_.ignored_classes);
             if (std::isfinite(settings_.region_area) || std::isfinite(settings_.region_width) || std::isfinite(settings_.region_height))
                 ignore_large_nonzero_regions(*sample, settings_.region_area, settings_.region_width, settings_.region_height);
+            prepare_ns_ += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+            ++prepared_;
         }
         return sample;
     }
@@ -164,7 +175,11 @@ class CropFeeder {
             const auto& names = files_[rnd.get_random_32bit_number() % files_.size()];
             const std::shared_ptr<sample_type> full = cache_(names);
             if (!full->error.empty()) item.made.error = full->error;
-            else if (full->labeled_points_by_class.empty()) item.made.warning = "Warning: no labeled points in " + full->image_filenames.label_filename;
+            else if (settings_.device_sampling) {   // whether the image has a labelled point at all is known once the device has prepared it
+                item.made.spec = draw_picked_crop_spec(rnd, aug_, item.made.draw);
+                item.made.is_spec = item.made.is_picked = true;
+                item.full = full;
+            } else if (full->labeled_points_by_class.empty()) item.made.warning = "Warning: no labeled points in " + full->image_filenames.label_filename;
             else if (specs_only_) {
                 item.made.spec = draw_crop_spec(crop_side_, *full, -1, rnd, aug_);
                 item.made.is_spec = true;
@@ -185,6 +200,7 @@ class CropFeeder {
     anh_host::pipe<FeedItem> queue_;
     shared_lru_cache<image_filenames_type, std::shared_ptr<sample_type>, image_filenames_hash> cache_;
     std::atomic<bool> running_{true};
+    std::atomic<uint64_t> prepare_ns_{0}, prepared_{0};
     std::vector<std::thread> threads_;
 };
 
@@ -297,6 +313,7 @@ int run(const TrainSettings& s) {
     if (!s.devices.empty()) NetPimpl::SetDevices(s.devices);
     const bool device_crops = !s.host_crops && s.devices.size() <= 1;
     std::cout << "Mini-batches are cut " << (device_crops ? "on the device from HBM-resident full images" : "on the host by the loader threads") << std::endl;
+    if (s.device_sampling) std::cout << "Crop centres are drawn on the device" << std::endl;
 
     NetPimpl::TrainingNet trainer;
     if (s.precision == "fp32") NetPimpl::check(anh_trainer_set_precision(trainer.handle(), ANH_FP32));
@@ -325,7 +342,7 @@ int run(const TrainSettings& s) {
     // recently drawn image leaves when a new one would not fit, as the decoded images leave the reference's LRU cache
     // (--cached-image-count, annonet_train_main.cpp:301,504-518); an image of the mini-batch being assembled is never the one to go
     NetPimpl::Dataset hbm_images;
-    struct Resident { int index; uint64_t bytes; std::list<std::string>::iterator at; };
+    struct Resident { int index; uint64_t bytes; std::list<std::string>::iterator at; bool drawable; };   // drawable: a labelled point exists (--device-sampling)
     std::unordered_map<std::string, Resident> hbm_index;
     std::list<std::string> hbm_lru;                                  // front = most recently drawn
     std::unordered_set<std::string> batch_keys;
@@ -335,11 +352,13 @@ int run(const TrainSettings& s) {
     std::vector<NetPimpl::input_type> images;
     std::vector<NetPimpl::training_label_type> labels;
     std::vector<anh_crop_spec> specs;
+    std::vector<anh_crop_draw> draws;
+    uint64_t device_prepare_ns = 0, device_prepared = 0;
     size_t step = 0;
     const double total_downscaling = s.initial_downscaling * s.further_downscaling;
     try {
         while (trainer.GetLearningRate() >= s.min_learning_rate && !(s.has_max_steps && step >= s.max_steps)) {   // :569-577,583
-            images.clear(); labels.clear(); specs.clear(); batch_keys.clear();
+            images.clear(); labels.clear(); specs.clear(); draws.clear(); batch_keys.clear();
             while ((device_crops ? specs.size() : images.size()) < s.minibatch) {
                 FeedItem item = feeder.next();
                 if (!item.made.error.empty()) throw std::runtime_error(item.made.error);
@@ -362,17 +381,31 @@ int run(const TrainSettings& s) {
                             ++hbm_evictions;
                         }
                         hbm_lru.push_front(key);
-                        at = hbm_index.emplace(key, Resident{hbm_images.Add(item.full->input_image, item.full->label_image), bytes, hbm_lru.begin()}).first;
+                        at = hbm_index.emplace(key, Resident{hbm_images.Add(item.full->input_image, item.full->label_image), bytes, hbm_lru.begin(), true}).first;
+                        if (item.made.is_picked) {   // both label filters and the point index, once per image, on its resident label map
+                            const auto t0 = std::chrono::steady_clock::now();
+                            const anh_dataset_info info = hbm_images.Prepare(at->second.index, s.ignored_classes, s.region_area, s.region_width, s.region_height, receptive_field);
+                            device_prepare_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+                            ++device_prepared;
+                            at->second.drawable = info.present > 0;
+                        }
                     } else hbm_lru.splice(hbm_lru.begin(), hbm_lru, at->second.at);
+                    if (!at->second.drawable) {   // stays resident, so that it is not prepared again at every draw
+                        const std::string warning = "Warning: no labeled points in " + item.full->image_filenames.label_filename;
+                        if (!s.quiet_empty_labels && warned.insert(warning).second) std::cout << warning << std::endl;
+                        continue;
+                    }
                     batch_keys.insert(key);
                     item.made.spec.image = at->second.index;
                     specs.push_back(item.made.spec);
+                    if (item.made.is_picked) draws.push_back(item.made.draw);
                 } else {
                     images.push_back(std::move(item.made.input_image));
                     labels.push_back(std::move(item.made.label_image));
                 }
             }
-            if (device_crops) trainer.StartTrainingOnCrops(hbm_images, specs, crop_side, s.class_weight, s.image_weight);
+            if (s.device_sampling) trainer.StartTrainingOnPickedCrops(hbm_images, specs, draws, crop_side, s.class_weight, s.image_weight);
+            else if (device_crops) trainer.StartTrainingOnCrops(hbm_images, specs, crop_side, s.class_weight, s.image_weight);
             else trainer.StartTraining(images, labels);
             if (step++ % s.save_interval == 0) save_inference_net(trainer, classes_json, total_downscaling);
             if (validation && step % s.validation_interval == 0) validation->report(trainer, step);
@@ -386,6 +419,10 @@ int run(const TrainSettings& s) {
     feeder.stop();
     save_inference_net(trainer, classes_json, total_downscaling);
     std::cout << "steps: " << step << ", " << feeder.statistics(hbm_index.size()) << ", HBM evictions: " << hbm_evictions << std::endl;
+    if (s.device_sampling)
+        std::cout << "mean preparation time per decoded image: " << (device_prepared ? 1e-6 * (double)device_prepare_ns / (double)device_prepared : 0.0) << " ms (device: Dataset::Prepare, "
+                  << device_prepared << " images)" << std::endl;
+    else std::cout << "mean preparation time per decoded image: " << feeder.preparation_ms_mean() << " ms (host: point lists and the two label filters)" << std::endl;
     return 0;
 }
 

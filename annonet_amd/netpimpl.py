@@ -175,6 +175,65 @@ class Dataset:
         check(self.L.anh_dataset_crop_batch(self.h, self._specs(specs), n, dim, classes, class_weight, image_weight, _ptr(img), _ptr(wl)))
         return img, wl["label"].copy(), wl["weight"].copy()
 
+    # ---- preparation and crop-centre sampling on the device ----
+    def prepare(self, index, classes_to_ignore=(), by_area=float("inf"), by_width=float("inf"), by_height=float("inf"), receptive_field_side=1):
+        """ignore_classes_to_ignore + ignore_large_nonzero_regions (annonet_train_main.cpp:414-502) on the resident label image, then its point
+        index.  -> dict(ignored_by_class, ignored_by_size, classes (ascending), counts)"""
+        ign = np.ascontiguousarray(list(classes_to_ignore), dtype=np.uint16)
+        info = _lib.DatasetInfo()
+        check(self.L.anh_dataset_prepare(self.h, int(index), _ptr(ign) if ign.size else None, int(ign.size), float(by_area), float(by_width), float(by_height),
+                                         int(receptive_field_side), C.byref(info)))
+        return {"ignored_by_class": info.ignored_by_class, "ignored_by_size": info.ignored_by_size,
+                "classes": [int(info.classes[i]) for i in range(info.present)], "counts": [int(info.counts[i]) for i in range(info.present)], "info": info}
+
+    def scratch_bytes(self):
+        """bytes of prepare()'s scratch the dataset holds (index counts; with a finite size limit also parents, blob map, region table)"""
+        n = C.c_uint64()
+        check(self.L.anh_dataset_scratch_bytes(self.h, C.byref(n)))
+        return int(n.value)
+
+    def labels(self, index, shape):
+        """the resident label image as it stands; shape = (height, width) as added"""
+        out = np.empty(shape, dtype=np.uint16)
+        check(self.L.anh_dataset_labels(self.h, int(index), _ptr(out)))
+        return out
+
+    @staticmethod
+    def _draws(draws):
+        arr = (_lib.CropDraw * len(draws))()
+        for a, d in zip(arr, draws):   # (class draw, point draw, rect draw x, rect draw y)
+            a.class_draw, a.point_draw, a.rect_draw_x, a.rect_draw_y = int(d[0]), int(d[1]), int(d[2]), int(d[3])
+        return arr
+
+    @staticmethod
+    def _picks(arr):
+        return [(p.label, p.x, p.y, p.left, p.top) for p in arr]
+
+    def pick(self, specs, draws, dim):
+        """-> [(label, x, y, left, top)]: the pixel each draw selects and the corner of the rectangle drawn around it"""
+        assert len(specs) == len(draws)
+        out = (_lib.CropPick * len(specs))()
+        check(self.L.anh_dataset_pick(self.h, self._specs(specs), self._draws(draws), len(specs), dim, out))
+        return self._picks(out)
+
+    def crop_batch_picked(self, specs, draws, dim, classes, class_weight=0.5, image_weight=0.5):
+        """crop_batch with the rectangles picked on the device (the specs' left / top are ignored) -> (images, labels, weights, picks)"""
+        assert len(specs) == len(draws)
+        n = len(specs)
+        shape = (n, dim, dim) if self.channels == 1 else (n, dim, dim, self.channels)
+        img = np.empty(shape, dtype=np.uint8)
+        wl = np.empty((n, dim, dim), dtype=WLABEL)
+        picks = (_lib.CropPick * n)()
+        check(self.L.anh_dataset_crop_batch_picked(self.h, self._specs(specs), self._draws(draws), n, dim, classes, class_weight, image_weight, _ptr(img), _ptr(wl), picks))
+        return img, wl["label"].copy(), wl["weight"].copy(), self._picks(picks)
+
+
+def resolve_pick(info, class_draw, point_draw):
+    """annonet_train_main.cpp:121,131 on an anh_dataset_info (Dataset.prepare(...)["info"]): -> (label, k)"""
+    label, k = C.c_uint16(), C.c_uint64()
+    check(_lib.lib().anh_resolve_pick(C.byref(info), class_draw, point_draw, C.byref(label), C.byref(k)))
+    return label.value, k.value
+
 
 def dnn_envelope_pack(anno_classes_json, downscaling_factor, serialized_runtime_net):
     """The bytes of annonet.dnn (annonet_train_main.cpp:557-565): dlib serialize of (string, double, string)."""
@@ -1056,6 +1115,12 @@ class TrainingNet(_Profiled):
     def StartTrainingOnCrops(self, dataset, specs, dim, class_weight=0.5, image_weight=0.5):
         """StartTraining on crops cut on the device from `dataset` (no host mini-batch)."""
         check(self.L.anh_trainer_step_crops(self.h, dataset.h, Dataset._specs(specs), len(specs), dim, class_weight, image_weight))
+
+    def StartTrainingOnPickedCrops(self, dataset, specs, draws, dim, class_weight=0.5, image_weight=0.5):
+        """StartTrainingOnCrops with every rectangle picked on the device from the image's point index (Dataset.prepare)."""
+        if len(specs) != len(draws):
+            raise AnnonetHipError(1, "one draw per crop spec")
+        check(self.L.anh_trainer_step_crops_picked(self.h, dataset.h, Dataset._specs(specs), Dataset._draws(draws), len(specs), dim, class_weight, image_weight))
 
     def forward_backward_device(self, d_images, d_labels, d_weights, n, h, w, loss_scale_n):
         check(self.L.anh_trainer_forward_backward_device(self.h, d_images, d_labels, d_weights, n, h, w, float(loss_scale_n)))

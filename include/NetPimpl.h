@@ -263,6 +263,13 @@ class Dataset {
     }
     void Remove(int index) { check(anh_dataset_remove(h_, index)); }   // frees that image's HBM; the index is reused by a later Add
     uint64_t ResidentBytes() const { uint64_t n = 0; check(anh_dataset_resident_bytes(h_, &n)); return n; }
+    // ignore_classes_to_ignore + ignore_large_nonzero_regions (annonet_train_main.cpp:414-502) on the resident label image, then the index
+    // TrainingNet::StartTrainingOnPickedCrops draws its crop centres from; info.present == 0: no labelled point in this image
+    anh_dataset_info Prepare(int index, const std::vector<uint16_t>& classes_to_ignore, double by_area, double by_width, double by_height, int receptive_field_side) {
+        anh_dataset_info info;
+        check(anh_dataset_prepare(h_, index, classes_to_ignore.data(), (int)classes_to_ignore.size(), by_area, by_width, by_height, receptive_field_side, &info));
+        return info;
+    }
     anh_dataset* handle() const { return h_; }
 
   private:
@@ -312,6 +319,13 @@ class TrainingNet {
     void StartTrainingOnCrops(const Dataset& dataset, const std::vector<anh_crop_spec>& crops, int dim, double class_weight, double image_weight) {
         if (crops.empty()) throw std::runtime_error("annonet_hip: empty mini-batch");
         check(anh_trainer_step_crops(h_, dataset.handle(), crops.data(), (int)crops.size(), dim, class_weight, image_weight));
+    }
+    // the same step with every crop's rectangle picked on the device around "the k-th labelled point of the j-th class" (:121-131) of its
+    // image, from the draws alone (Dataset::Prepare built the index); the crops' left / top are ignored
+    void StartTrainingOnPickedCrops(const Dataset& dataset, const std::vector<anh_crop_spec>& crops, const std::vector<anh_crop_draw>& draws, int dim, double class_weight,
+                                    double image_weight) {
+        if (crops.empty() || crops.size() != draws.size()) throw std::runtime_error("annonet_hip: crops and draws must be non-empty and of equal size");
+        check(anh_trainer_step_crops_picked(h_, dataset.handle(), crops.data(), draws.data(), (int)crops.size(), dim, class_weight, image_weight));
     }
     RuntimeNet GetRuntimeNet(int precision = ANH_BF16) const {  // :558, by value
         anh_runtime* rt = nullptr;

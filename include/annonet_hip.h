@@ -619,6 +619,54 @@ int anh_dataset_crop_batch(anh_dataset* d, const anh_crop_spec* specs, int n, in
                            uint8_t* images, anh_wlabel* labels);
 /* StartTraining on n crops cut on the device: the mini-batch never exists on the host */
 int anh_trainer_step_crops(anh_trainer* h, anh_dataset* d, const anh_crop_spec* specs, int n, int dim, double class_weight, double image_weight);
+/* ---- dataset preparation and crop-centre sampling on the device (opt-in; the calls above keep their behaviour) ----
+   What the reference does once per decoded image on the host — ignore_classes_to_ignore (annonet_train_main.cpp:414-424),
+   ignore_large_nonzero_regions (:434-502) and the labelled-point lists of decode_rgba_label_image (annonet.cpp:41-58), kept only so that
+   randomly_crop_image can take "the k-th labelled point of the j-th class" (annonet_train_main.cpp:121-131) — runs on the resident label
+   image instead.  No point list exists: an index of 4 bytes per PRESENT class and 1024 pixels answers "the k-th pixel of class c in
+   raster order", the order in which the reference pushes its points.
+   anh_dataset_prepare, on the labels of image `index` as they stand, in place:
+     1. labels equal to one of classes_to_ignore[0..n_ignore), n_ignore <= 64, become ANH_LABEL_IGNORE; info->ignored_by_class = pixels changed;
+     2. unless all three limits are infinite: the blobs of kernels_blobs.hip (8-connected, equal non-zero label) with
+        (double)area > by_area * rf^2, (double)width > by_width * rf or (double)height > by_height * rf (rf = receptive_field_side; the
+        products in double, as anh_ignore_large_nonzero_regions forms them; strict; infinity = that test off) become ANH_LABEL_IGNORE;
+        info->ignored_by_size = pixels changed that were not ANH_LABEL_IGNORE before — the map and the count anh_ignore_large_nonzero_regions gives;
+     3. the index: a label >= 64 that is not ANH_LABEL_IGNORE is ANH_ERR_INVALID (the crop path's own limit) and leaves the image
+        unprepared; info->classes[0..present) = the class values present, ASCENDING, counts[i] = pixels of classes[i].
+   A call that fails after its first launch (such a label, the blob labeller's limits, ANH_ERR_OOM for the region table or the index) may
+   already have applied one or both filters to the resident labels: they are rewritten in place, and the image is left unprepared.
+   The call waits for the dataset's stream before it touches the labels (as anh_dataset_remove does) and again before it returns.  It may be
+   called again (the filters then see the labels as they stand; the index is rebuilt).  The index, 4 * present * ceil(height * width / 1024)
+   bytes, is added to anh_dataset_resident_bytes; anh_dataset_remove subtracts it.
+   Scratch of the dataset, reused by every call and reserved before the first launch: 0.25 bytes per pixel for the index; with a finite
+   limit another 8 bytes per pixel (union-find parents and the blob map, 4 each), also reserved before the first launch, plus a region
+   table of 56 bytes per blob, reserved once the labelling's blob count is back (the labelling does not need it), before the size filter
+   has changed anything.  All limits infinite: no blob scratch is reserved.  anh_dataset_scratch_bytes: the bytes of this scratch the
+   dataset holds at the moment (it only grows). */
+typedef struct { int64_t ignored_by_class, ignored_by_size; int present; uint16_t classes[64]; uint64_t counts[64]; } anh_dataset_info;
+/* classes[0..present) ascending, counts[i] = labelled pixels of classes[i] after both filters; present == 0: nothing to draw from */
+int anh_dataset_prepare(anh_dataset* d, int index, const uint16_t* classes_to_ignore, int n_ignore,
+                        double by_area, double by_width, double by_height, int receptive_field_side, anh_dataset_info* info);
+int anh_dataset_scratch_bytes(const anh_dataset* d, uint64_t* bytes);
+int anh_dataset_labels(anh_dataset* d, int index, uint16_t* labels);            /* the resident label image as it stands (tests, hosts that want it back) */
+/* The random draws of a crop centre (annonet_train_main.cpp:121,131 and random_rect_containing_point), in the reference's order */
+typedef struct { uint32_t class_draw; uint64_t point_draw; uint32_t rect_draw_x, rect_draw_y; } anh_crop_draw;
+typedef struct { uint16_t label; int32_t x, y; long left, top; } anh_crop_pick;
+/* label = classes[class_draw % present], k = point_draw % counts[that slot] (64-bit).  The class order is ascending class value, where the
+   reference iterates an unordered_map (implementation-defined order): both are uniform over the present classes.  Host logic, no GPU;
+   ANH_ERR_INVALID for present outside 1..64 or an empty class. */
+int anh_resolve_pick(const anh_dataset_info* info, uint32_t class_draw, uint64_t point_draw, uint16_t* label, uint64_t* k);
+/* out[i] = the k-th pixel (x, y) of the resolved class of image specs[i].image in raster order, and the corner of
+   anh_random_rect_containing_point(rect_draw_x, rect_draw_y, x, y, side, side), side = round(dim * further_downscaling_factor).  The library
+   resolves on the host from the info it kept at prepare time; the device receives (label, k, the two rect draws).  Waits for the result. */
+int anh_dataset_pick(anh_dataset* d, const anh_crop_spec* specs, const anh_crop_draw* draws, int n, int dim, anh_crop_pick* out);
+/* anh_dataset_crop_batch / anh_trainer_step_crops with the rectangle picked on the device: specs[i].left / .top are ignored, everything else
+   in a spec means what it means there; the picked corner goes straight into the crop kernel's argument and never visits the host (picks,
+   when given, receives it all the same).  ANH_ERR_INVALID for an image that is not prepared or has present == 0. */
+int anh_dataset_crop_batch_picked(anh_dataset* d, const anh_crop_spec* specs, const anh_crop_draw* draws, int n, int dim, int classes,
+                                  double class_weight, double image_weight, uint8_t* images, anh_wlabel* labels, anh_crop_pick* picks /* nullable */);
+int anh_trainer_step_crops_picked(anh_trainer* h, anh_dataset* d, const anh_crop_spec* specs, const anh_crop_draw* draws, int n, int dim,
+                                  double class_weight, double image_weight);
 
 /* ignore_large_nonzero_regions (annonet_train_main.cpp:434-502), in place on a u16 label image: 8-connected blobs of equal
    non-zero, non-ignored label larger than by_area * rf^2 pixels, wider than by_width * rf or taller than by_height * rf
